@@ -10,7 +10,14 @@ SDXL weights (seeded), N(0,1) text embeddings, trajectories from this build's ow
 rewards.  Multi-GPU: one process per GPU, pure data parallel (weak scaling); the LoRA gradient is all-reduced over RCCL in
 ~32 MB buckets issued during the backward of the window's last micro-step (GradBuckets), overlapped with it.
 
-Secondary objects on the same JSON line (never the headline value):
+A plain run does only what the headline needs: it builds the model, samples the buffer, warms up, times --steps
+steps and prints the result line.  --dump-outputs DIR also writes what the last timed step computed (dump_outputs).
+Everything below takes runs of its own and is measured only with --full.
+
+Secondary objects on the same JSON line with --full (never the headline value):
+  "roofline"  one extra profiled step: the dominant GEMM-family kernel against the MFMA peak;
+  "epoch"     --epochs full online epochs (sampling + VAE decode + PickScore + training);
+  "cpu_baseline"  the fp32 CPU oracle on a bounded sample of the same workload;
   "c3"        BASELINE configs[2] on this GPU: SDXL-DMD2 PSO, 4-step sampler (T = 3), full-UNet grads against a frozen
               reference UNet, 1 pair per micro-step -- its own warmed-up, timed steps + dominant-kernel roofline;
   "lora_bs1"  the north-star operating point "bs = 1 / GPU": the C2 LoRA step at 1 pair, gas 1 (one micro-step =
@@ -23,9 +30,10 @@ Secondary objects on the same JSON line (never the headline value):
   "dist"      (N > 1) the backend and world size torch.distributed really runs, every rank's ms/step, and the
               bucketed all-reduce: bytes on the wire, its time alone, and the part of it left exposed after the
               backward (the rest ran under the backward).
-  The config objects run at N = 1 only (--no-extra skips them).
+  The config objects run at N = 1 only.  With --full, --no-roofline / --epochs 0 / --no-cpu-baseline / --no-extra
+  each leave one part out again.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   Under torchrun (RANK / WORLD_SIZE / LOCAL_RANK set) every process is one rank.  Started directly with --gpus N > 1,
   bench.py launches `python -m torch.distributed.run --nproc-per-node N ... bench.py` as a child BEFORE any GPU call
   and exits with its code, so both launch forms measure N GPUs.
@@ -80,6 +88,12 @@ def parse():
     ap.add_argument("--cpu-timed", type=int, default=3, help="timed CPU-baseline samples after one warm-up")
     ap.add_argument("--no-extra", action="store_true", help="skip the c3 / lora_bs1 / c5 secondary objects")
     ap.add_argument("--extra-steps", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline, each in runs of its own: roofline, epoch "
+                         "metric, CPU baseline, the c3 / lora_bs1 / dmd_lora / turbo_ref / c5 / vae objects and (N > 1) "
+                         "the dist object; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (dump_outputs)")
     return ap.parse_args()
 
 
@@ -134,6 +148,32 @@ def one_step(tr, buf, g, graph=False):
         tr.train_epoch_graph(sb)
     else:
         tr.train_epoch(sb)
+
+
+DUMP_MAX_ELEMS = 12 * 2 ** 20   # fp32 elements of the trained buffer written by --dump-outputs (48 MB of the 64 MB cap)
+
+
+def dump_outputs(out_dir, tr, n_last):
+    """--dump-outputs DIR: what a caller of the timed path holds after the last timed step, as float32 .npy files.
+      loss.npy       the n_last pass losses the last step appended to tr.loss_hist (one per batched UNet pass);
+      grad_clip.npy  (global gradient norm, clip coefficient) of the last optimizer step -- the gradient itself is
+                     zeroed by the step, this is what is left of it;
+      params.npy     the trained fp32 master buffer after the step (flat LoRA bucket, or every UNet parameter with
+                     --full-unet); above DUMP_MAX_ELEMS elements a fixed sample: the sorted indices drawn by a CPU
+                     generator seeded 0, the same for every run and build.
+    Model weights, text embeddings, trajectories, rewards and shuffles all come from fixed seeds, so two runs with
+    the same arguments train on identical inputs."""
+    import numpy as np
+    from pairwise_sample_optimization_amd.trainer import trainable
+    os.makedirs(out_dir, exist_ok=True)
+    master = trainable(tr.unet)[0].detach().reshape(-1)
+    if master.numel() > DUMP_MAX_ELEMS:
+        idx = torch.randint(0, master.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(0))
+        master = master[idx.sort().values.to(master.device)]
+    out = {"loss": torch.stack([l.detach().reshape(()) for l in tr.loss_hist[-n_last:]]) if n_last else torch.zeros(0),
+           "grad_clip": tr.clip_buf, "params": master}
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def src_hash():
@@ -515,6 +555,7 @@ def main():
     if tr.buckets is not None:
         tr.buckets.timing = True
         tr.buckets.exposed_ms = []
+    n_loss0 = len(tr.loss_hist)
     t0 = time.perf_counter()
     for i in range(args.steps):
         one_step(tr, buf, g, graph=args.graph)
@@ -526,6 +567,8 @@ def main():
     dt = max_over_ranks(dt_rank, dev)
     if tr.buckets is not None:
         tr.buckets.timing = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, (len(tr.loss_hist) - n_loss0) // max(args.steps, 1))
     imgs_per_step_gpu = 2 * args.pairs * args.gas * (args.num_steps - 1)
     value = imgs_per_step_gpu * world * args.steps / dt
     ms = dt / args.steps * 1e3
@@ -555,17 +598,18 @@ def main():
         res["step_mfma_frac"] = round(step_tf / (ms * 1e-3) / PEAK_BF16_TFLOPS, 4)
         res["step_tflop_executed"] = round(step_tf, 2)
         res["skipped_ref_prefix_tflop_per_step"] = round(skip, 3)
-    if world > 1:
+    # everything below takes runs of its own beside the timed steps: --full only
+    if args.full and world > 1:
         res["dist"] = dist_report(tr, dev, dt_rank, args.steps)
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         res["roofline"] = roofline(tr, buf, g)
-    if args.epochs > 0:
+    if args.full and args.epochs > 0:
         log("[bench] epoch metric ...")
         res["epoch"] = epoch_metric(args, dev, tr, buf, g, args.epochs)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("[bench] cpu baseline ...")
         res["cpu_baseline"] = cpu_baseline(args, unet)
-    if world == 1 and not args.no_extra and not args.full_unet and args.res == 1024:
+    if args.full and world == 1 and not args.no_extra and not args.full_unet and args.res == 1024:
         del unet, tr, buf
         torch.cuda.empty_cache()
         log("[bench] lora_bs1 ...")

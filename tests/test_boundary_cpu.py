@@ -1,14 +1,14 @@
 """The diffusers / config boundary on CPU (no kernels run): from_config(dict) honours and validates the diffusers
 config keys, save_pretrained -> from_pretrained(path, subfolder=...) round-trips a synthetic model directory
-(config.json + safetensors), and the reference's own run configs load unchanged through the ml_collections
-stand-in (when /root/reference is present: the build container only)."""
+(config.json + safetensors), and run configs in the reference's format, holding the reference's recorded values
+(tests/golden/run_config_*.json, tools/make_golden.py), load through the ml_collections stand-in."""
 import json
 import os
 
 import pytest
 import torch
 
-REF_CFG = "/root/reference/human_preference_tuning/config"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def test_unet_from_config_diffusers_dict_roundtrip():
@@ -55,13 +55,34 @@ def test_unet_and_vae_save_from_pretrained_roundtrip(tmp_path):
         UNet2DConditionModel.from_pretrained("stabilityai/sdxl-turbo", subfolder="unet")  # a hub id: no network
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference configs live in the build container only")
+def _write_run_config(path, values):
+    """A run config file in the reference's format (`import ml_collections`, `get_config()` filling a ConfigDict
+    field by field, nested ConfigDicts for the sections) holding the recorded values."""
+    lines = ["import ml_collections", "", "", "def get_config():", "    config = ml_collections.ConfigDict()"]
+
+    def emit(prefix, d):
+        for k, v in d.items():
+            if isinstance(v, dict) and v:
+                lines.append(f"    {prefix}.{k} = ml_collections.ConfigDict()")
+                emit(f"{prefix}.{k}", v)
+            else:
+                lines.append(f"    {prefix}.{k} = {v!r}")
+
+    emit("config", values)
+    lines += ["    return config", ""]
+    with open(path, "w") as f:
+        f.write("\n".join(lines))
+
+
 @pytest.mark.parametrize("name,ours", [("config_sdxl_turbo_dpo.py", "config_sdxl_turbo_dpo"),
                                        ("config_sdxl_dmd_dpo.py", "config_sdxl_dmd_dpo")])
-def test_reference_run_configs_load_unchanged(name, ours):
+def test_reference_run_configs_load_unchanged(name, ours, tmp_path):
     import importlib
     from pairwise_sample_optimization_amd.config import load_config_file, apply_overrides
-    ref = load_config_file(os.path.join(REF_CFG, name))
+    values = json.load(open(os.path.join(GOLDEN, f"run_config_{ours}.json")))
+    _write_run_config(tmp_path / name, values)
+    ref = load_config_file(str(tmp_path / name))
+    assert ref.to_dict() == values
     mine = importlib.import_module(f"pairwise_sample_optimization_amd.config.{ours}").get_config()
     # every key the trainers read (SURVEY §2) has the reference's value in the package's own config module
     for k in ("seed", "num_epochs", "checkpointing_steps", "mixed_precision"):

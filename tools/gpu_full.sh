@@ -6,6 +6,7 @@ set -u
 mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 STEPS=${BENCH_STEPS:-5}
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the first bench run is the one with roofline + cpu_baseline
 if [ "${SKIP_TESTS:-0}" != 1 ]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -q -s --timeout 300 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1; rc=$?
   echo "pytest rc=$rc"; grep -E "passed|failed|Error" gpurun_out/pytest_gpu.log | tail -15

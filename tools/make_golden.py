@@ -368,7 +368,25 @@ def make_dmd_replay(mod, dtype, P, hw, seed, t_int, beta=50.0, eps=0.1):
     return out
 
 
+def make_run_configs():
+    """The values of the reference's two run configs (settings only), read through the package's ml_collections
+    stand-in -> tests/golden/run_config_<name>.json (tests/test_boundary_cpu.py rebuilds a config file from them)."""
+    import json
+    from pairwise_sample_optimization_amd.config import load_config_file
+    names = []
+    for name in ("config_sdxl_turbo_dpo", "config_sdxl_dmd_dpo"):
+        cfg = load_config_file(os.path.join(REF, "human_preference_tuning", "config", name + ".py"))
+        with open(os.path.join(OUT, f"run_config_{name}.json"), "w") as f:
+            json.dump(cfg.to_dict(), f, indent=1, sort_keys=True)
+            f.write("\n")
+        names.append(f"run_config_{name}.json")
+    return names
+
+
 def main():
+    if sys.argv[1:] == ["configs"]:  # only the run-config values (no reference step function is imported)
+        print("\n".join(make_run_configs()))
+        return
     _install_stub()
     turbo = _load("turbo_inference_with_logprob.py", "ref_turbo_step")
     dmd = _load("distilled_inference_with_logprob.py", "ref_dmd_step")
@@ -399,6 +417,7 @@ def main():
     for name, out in extra.items():
         np.savez_compressed(os.path.join(OUT, name), **out)
         cases.append(name)
+    cases += make_run_configs()
     print("\n".join(cases))
 
 
