@@ -10,6 +10,10 @@
  *   - Plain pointers and sizes only; no framework types.  Every device buffer (weights, activations, workspace) is
  *     owned by the caller; the library never allocates on the hot path.
  *   - bf16 tensors are raw uint16 bit patterns; activations are channels-last (NHWC / [tokens][channels]).
+ *   - The 16-bit element type is fixed per library at compile time: libpso_amd.so is bf16, libpso_amd_f16.so (the
+ *     same sources with -DPSO_ELEM_F16) is IEEE fp16; pso_elem_dtype() tells which.  Wherever this header or a
+ *     function name says "bf16" it means "the library's 16-bit element type".  Accumulators, statistics, softmax
+ *     state, optimizer state and LoRA gradients are fp32 in both.
  *   - Every function returns 0 (PSO_OK) or an error code; pso_last_error() gives a thread-local message.
  *   - Work is enqueued on the caller's hipStream_t (pass the stream handle as void*); nothing synchronises, so every
  *     call is capturable into a hipGraph.
@@ -34,7 +38,11 @@ extern "C" {
 /* dtype codes */
 #define PSO_F32 0
 #define PSO_BF16 1
-#define PSO_U8 2 /* uint8 images (pso_clip_preprocess only) */
+#define PSO_F16 2
+#define PSO_U8 2 /* uint8 images: the meaning of code 2 for pso_clip_preprocess's img_dtype, and only there -- in both
+                  * libraries, so the f16 library takes f32 and uint8 images at that entry, never fp16 ones */
+/* Every entry that takes a dtype code accepts PSO_F32 and pso_elem_dtype(); the other 16-bit code returns PSO_ERR_ARG
+ * with a message naming the library to load. */
 
 /* step modes */
 #define PSO_MODE_TURBO 0 /* Euler-ancestral (SDXL-Turbo)   DP/turbo_inference_with_logprob.py:24-116 */
@@ -44,7 +52,7 @@ extern "C" {
  * dtype, :129-135 the log-density in that dtype).  These modes round every intermediate to that
  * dtype in the reference's operation order (values stay fp32 in memory, holding fp16 / bf16-representable numbers),
  * and the loss stage rounds Δ, exp, the clipped ratio, its log and beta*log to it (T:844-850 on latent-dtype
- * log-probs).  The coefficients of these modes are the latent-dtype values of the reference (pso_core.dmd_coef). */
+ * log-probs).  The latent dtype is the mode's, in either library: it does not follow pso_elem_dtype().  The coefficients of these modes are the latent-dtype values of the reference (pso_core.dmd_coef). */
 #define PSO_MODE_DMD_F16 2
 #define PSO_MODE_DMD_BF16 3
 
@@ -60,6 +68,8 @@ extern "C" {
 
 const char* pso_last_error(void);
 int pso_abi_version(void);
+/* PSO_BF16 (libpso_amd.so) or PSO_F16 (libpso_amd_f16.so): the 16-bit element type this library was compiled for. */
+int pso_elem_dtype(void);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * PSO step log-prob (one scheduler step for a batch of B latents of n elements each).

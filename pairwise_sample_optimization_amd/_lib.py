@@ -13,11 +13,19 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # PSO_LIB=knobs selects the TOOLS build (libpso_amd_knobs.so: the same sources with the benchmark knobs of
 # include/pso_amd_knobs.h compiled in) for A/B measurements and the knob-pinned kernel-form tests; the product path
 # and everything else load libpso_amd.so, which has no knobs.  PSO_LIB_PATH: an explicit file (same-box A/B only).
+# PSO_LIB=f16 selects libpso_amd_f16.so: the same sources with IEEE fp16 as the 16-bit element type (-DPSO_ELEM_F16,
+# no knobs).  The element type is per process, as accelerate's `mixed_precision` is: one library, one ELEM_DTYPE.
 KNOBS = os.environ.get("PSO_LIB", "") == "knobs"
-LIB_PATH = os.environ.get("PSO_LIB_PATH") or os.path.join(_HERE, "libpso_amd_knobs.so" if KNOBS else "libpso_amd.so")
+F16 = os.environ.get("PSO_LIB", "") == "f16"
+LIB_PATH = os.environ.get("PSO_LIB_PATH") or os.path.join(
+    _HERE, "libpso_amd_knobs.so" if KNOBS else "libpso_amd_f16.so" if F16 else "libpso_amd.so")
 
 PSO_F32 = 0
 PSO_BF16 = 1
+PSO_F16 = 2
+# the library's 16-bit element type (checked against pso_elem_dtype() at load)
+ELEM_DTYPE = torch.float16 if F16 else torch.bfloat16
+ELEM_CODE = PSO_F16 if F16 else PSO_BF16
 MODE_TURBO = 0
 MODE_DMD = 1
 MODE_DMD_F16 = 2   # DMD2 latent-dtype replay modes (include/pso_amd.h PSO_MODE_DMD_F16 / _BF16)
@@ -44,6 +52,7 @@ cl = ctypes.c_long
 SIGNATURES = {
     "pso_last_error": (ctypes.c_char_p, []),
     "pso_abi_version": (ci, []),
+    "pso_elem_dtype": (ci, []),
     "pso_step_logprob_ws_bytes": (csz, [ci, ci]),
     "pso_step_logprob": (ci, [ci, ci, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, csz, vp]),
     "pso_pair_loss_ws_bytes": (csz, [ci, ci]),
@@ -172,6 +181,14 @@ def require_knobs(what):
                           "library libpso_amd.so has none")
 
 
+def require_bf16(what):
+    """Paths that were verified against their oracles in bf16 only raise under the f16 library instead of running
+    unverified: the fp8 forward, full-UNet training, clip.py."""
+    if F16:
+        raise PsoLibError(f"{what} is not supported by the f16 library (PSO_LIB=f16, libpso_amd_f16.so): unset "
+                          "PSO_LIB and run it on the bf16 library")
+
+
 def lib():
     """Load (once) and return the bound library; raises if it is absent."""
     global _lib
@@ -181,6 +198,10 @@ def lib():
                               "(no CPU fallback exists)")
         l = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         _bind(l)
+        if l.pso_elem_dtype() != ELEM_CODE:
+            raise PsoLibError(f"{LIB_PATH} has 16-bit element code {l.pso_elem_dtype()}, but PSO_LIB="
+                              f"{os.environ.get('PSO_LIB', '')!r} expects {ELEM_CODE} ({ELEM_DTYPE}): PSO_LIB=f16 goes "
+                              "with libpso_amd_f16.so, everything else with a bf16 library")
         _lib = l
     return _lib
 
@@ -202,8 +223,12 @@ def ptr(t):
 def dtype_code(t):
     if t.dtype == torch.float32:
         return PSO_F32
-    if t.dtype == torch.bfloat16:
-        return PSO_BF16
+    if t.dtype == ELEM_DTYPE:
+        return ELEM_CODE
+    if t.dtype in (torch.float16, torch.bfloat16):
+        raise PsoLibError(f"{t.dtype} tensor, but the loaded library's 16-bit element type is {ELEM_DTYPE} "
+                          f"({os.path.basename(LIB_PATH)}): " + ("unset PSO_LIB for the bf16 library" if F16 else
+                          "set PSO_LIB=f16 for libpso_amd_f16.so") + "; the element type is per process")
     raise PsoLibError(f"unsupported dtype {t.dtype}")
 
 

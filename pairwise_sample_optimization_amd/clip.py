@@ -27,6 +27,7 @@ from types import SimpleNamespace
 import torch
 import torch.nn as nn
 
+from . import _lib
 from . import kernels as K
 from .unet import Linear, Norm, _param
 
@@ -178,6 +179,7 @@ class _TextEmbeddings(nn.Module):
 class CLIPTextTransformer(nn.Module):
     def __init__(self, cfg: CLIPTextConfig):
         super().__init__()
+        _lib.require_bf16("clip.py (CLIPTextTransformer: PickScore and the text encoders)")
         self.cfg = cfg
         self.embeddings = _TextEmbeddings(cfg)
         self.encoder = CLIPEncoder(cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads,
@@ -367,6 +369,7 @@ class _ConvNoBias(nn.Module):
 class CLIPVisionTransformer(nn.Module):
     def __init__(self, cfg: CLIPVisionConfig):
         super().__init__()
+        _lib.require_bf16("clip.py (CLIPVisionTransformer: PickScore and the text encoders)")
         self.cfg = cfg
         self.embeddings = _VisionEmbeddings(cfg)
         self.pre_layrnorm = Norm(cfg.hidden_size)

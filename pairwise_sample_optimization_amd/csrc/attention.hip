@@ -188,7 +188,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_fwd_kernel(AttnArgs a, in
   // of its query without a VALU add per score or a cross-lane reduction; it sums the bf16 P the PV product uses
   f32x4 lsum[QI];
   float m_run[QI];
-  const bf16x8 ones = __builtin_bit_cast(bf16x8, make_uint4(0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u));
+  const bf16x8 ones = __builtin_bit_cast(bf16x8, make_uint4(PSO_ELEM_ONES2, PSO_ELEM_ONES2, PSO_ELEM_ONES2, PSO_ELEM_ONES2));
 #pragma unroll
   for (int qi = 0; qi < QI; ++qi) {
     m_run[qi] = -INFINITY;
@@ -216,8 +216,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_fwd_kernel(AttnArgs a, in
 #pragma unroll
       for (int qi = 0; qi < QI; ++qi) {
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[0], qf[qi][0], acc, 0, 0, 0);
-        s[qi][kj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[1], qf[qi][1], acc, 0, 0, 0);
+        acc = mfma16x16x32(kf[0], qf[qi][0], acc);
+        s[qi][kj] = mfma16x16x32(kf[1], qf[qi][1], acc);
       }
     }
     const int kbase = kt * ATT_KT;
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_fwd_kernel(AttnArgs a, in
 #pragma unroll
       for (int qi = 0; qi < QI; ++qi) {
         pf[qi] = pack_p(s[qi][2 * ks], s[qi][2 * ks + 1]);
-        if (MSUM) lsum[qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf[qi], lsum[qi], 0, 0, 0);
+        if (MSUM) lsum[qi] = mfma16x16x32(ones, pf[qi], lsum[qi]);
       }
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_fwd_kernel(AttnArgs a, in
         const s16x4 v1 = tr_read(v_img, (2 * ks + 1) * 16 + 4 * g, dt * 16, lane);
         const bf16x8 vf = cat_frag(v0, v1);
 #pragma unroll
-        for (int qi = 0; qi < QI; ++qi) o[qi][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qi], o[qi][dt], 0, 0, 0);
+        for (int qi = 0; qi < QI; ++qi) o[qi][dt] = mfma16x16x32(vf, pf[qi], o[qi][dt]);
       }
     }
   }
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_fwd2_kernel(AttnArgs a, i
   f32x4 o[QI][4];
   f32x4 lsum[QI];
   float m_run[QI];
-  const bf16x8 ones = __builtin_bit_cast(bf16x8, make_uint4(0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u));
+  const bf16x8 ones = __builtin_bit_cast(bf16x8, make_uint4(PSO_ELEM_ONES2, PSO_ELEM_ONES2, PSO_ELEM_ONES2, PSO_ELEM_ONES2));
 #pragma unroll
   for (int qi = 0; qi < QI; ++qi) {
     m_run[qi] = -INFINITY;
@@ -461,8 +461,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_fwd2_kernel(AttnArgs a, i
 #pragma unroll
       for (int qi = 0; qi < QI; ++qi) {
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[0], qf[qi][0], acc, 0, 0, 0);
-        s[qi][kj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[1], qf[qi][1], acc, 0, 0, 0);
+        acc = mfma16x16x32(kf[0], qf[qi][0], acc);
+        s[qi][kj] = mfma16x16x32(kf[1], qf[qi][1], acc);
       }
     }
     // V fragments of the first 32 keys: in flight during the softmax
@@ -531,13 +531,13 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_fwd2_kernel(AttnArgs a, i
 #pragma unroll
       for (int qi = 0; qi < QI; ++qi) {
         pf[qi] = pack_p(s[qi][2 * ks], s[qi][2 * ks + 1]);
-        lsum[qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf[qi], lsum[qi], 0, 0, 0);
+        lsum[qi] = mfma16x16x32(ones, pf[qi], lsum[qi]);
       }
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         const bf16x8 vf = ks == 0 ? cat_frag(vr0[2 * dt], vr0[2 * dt + 1]) : cat_frag(vr1[2 * dt], vr1[2 * dt + 1]);
 #pragma unroll
-        for (int qi = 0; qi < QI; ++qi) o[qi][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qi], o[qi][dt], 0, 0, 0);
+        for (int qi = 0; qi < QI; ++qi) o[qi][dt] = mfma16x16x32(vf, pf[qi], o[qi][dt]);
       }
     }
   };
@@ -754,10 +754,10 @@ __global__ __launch_bounds__(ATT_THREADS, KJ == 2 ? 2 : 1) void attn_bwd_dkv_ker
         for (int kj = 0; kj < KJ; ++kj) {
           // dP accumulates onto -delta (register r = query 4g + r), so dS = P * acc: one VALU op per score less
           f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, pacc = ndel;
-          sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa_[0], kf[kj][0], sacc, 0, 0, 0);
-          sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa_[1], kf[kj][1], sacc, 0, 0, 0);
-          pacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oa_[0], vf[kj][0], pacc, 0, 0, 0);
-          pacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oa_[1], vf[kj][1], pacc, 0, 0, 0);
+          sacc = mfma16x16x32(qa_[0], kf[kj][0], sacc);
+          sacc = mfma16x16x32(qa_[1], kf[kj][1], sacc);
+          pacc = mfma16x16x32(oa_[0], vf[kj][0], pacc);
+          pacc = mfma16x16x32(oa_[1], vf[kj][1], pacc);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float pr = fast_exp2(fmaf(sacc[r], c2, -lq[r]));
@@ -809,8 +809,8 @@ __global__ __launch_bounds__(ATT_THREADS, KJ == 2 ? 2 : 1) void attn_bwd_dkv_ker
       for (int dt = 0; dt < 4; ++dt) {
 #pragma unroll
         for (int kj = 0; kj < KJ; ++kj) {
-          dv[kj][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(of[dt], pack_p(p[0][kj], p[1][kj]), dv[kj][dt], 0, 0, 0);
-          dk[kj][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[dt], pack_p(dsv[0][kj], dsv[1][kj]), dk[kj][dt], 0, 0, 0);
+          dv[kj][dt] = mfma16x16x32(of[dt], pack_p(p[0][kj], p[1][kj]), dv[kj][dt]);
+          dk[kj][dt] = mfma16x16x32(qf[dt], pack_p(dsv[0][kj], dsv[1][kj]), dk[kj][dt]);
         }
       }
     }
@@ -1008,10 +1008,10 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_x_kernel(AttnArgs a) 
 #pragma unroll
         for (int kj = 0; kj < KJ; ++kj) {
           f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, pacc = ndel;
-          sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa_[0], kf[kj][0], sacc, 0, 0, 0);
-          sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa_[1], kf[kj][1], sacc, 0, 0, 0);
-          pacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oa_[0], vf[kj][0], pacc, 0, 0, 0);
-          pacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oa_[1], vf[kj][1], pacc, 0, 0, 0);
+          sacc = mfma16x16x32(qa_[0], kf[kj][0], sacc);
+          sacc = mfma16x16x32(qa_[1], kf[kj][1], sacc);
+          pacc = mfma16x16x32(oa_[0], vf[kj][0], pacc);
+          pacc = mfma16x16x32(oa_[1], vf[kj][1], pacc);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float pr = fast_exp2(fmaf(sacc[r], c2, -lq[r]));
@@ -1058,8 +1058,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_x_kernel(AttnArgs a) 
       for (int dt = 0; dt < 4; ++dt) {
 #pragma unroll
         for (int kj = 0; kj < KJ; ++kj) {
-          dv[kj][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(of[dt], pack_p(p[0][kj], p[1][kj]), dv[kj][dt], 0, 0, 0);
-          dk[kj][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[dt], pack_p(dsv[0][kj], dsv[1][kj]), dk[kj][dt], 0, 0, 0);
+          dv[kj][dt] = mfma16x16x32(of[dt], pack_p(p[0][kj], p[1][kj]), dv[kj][dt]);
+          dk[kj][dt] = mfma16x16x32(qf[dt], pack_p(dsv[0][kj], dsv[1][kj]), dk[kj][dt]);
         }
       }
     }
@@ -1077,7 +1077,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_x_kernel(AttnArgs a) 
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
           const bf16x8 kfr = cat_frag(tr_read(sK, r0, dt * 16, lane), tr_read(sK, r0 + 4, dt * 16, lane));
-          dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr, bfr, dq[dt], 0, 0, 0);
+          dq[dt] = mfma16x16x32(kfr, bfr, dq[dt]);
         }
       }
       const int qr = (qa + i) * ATT_KT + wave * 16 + c;
@@ -1279,8 +1279,8 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkv_pp_kernel(AttnArgs a, int
       const bf16x8 qf = cat_frag(qtr[qk][2 * dt], qtr[qk][2 * dt + 1]);
 #pragma unroll
       for (int kj = 0; kj < 2; ++kj) {
-        dv[kj][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(of, pP[qk][kj], dv[kj][dt], 0, 0, 0);
-        dk[kj][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, pS[qk][kj], dk[kj][dt], 0, 0, 0);
+        dv[kj][dt] = mfma16x16x32(of, pP[qk][kj], dv[kj][dt]);
+        dk[kj][dt] = mfma16x16x32(qf, pS[qk][kj], dk[kj][dt]);
       }
     }
   };
@@ -1315,10 +1315,10 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkv_pp_kernel(AttnArgs a, int
 #pragma unroll
       for (int kj = 0; kj < 2; ++kj) {
         f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, pacc = nd[qs];
-        sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0], kf[kj][0], sacc, 0, 0, 0);
-        S[qs][kj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[1], kf[kj][1], sacc, 0, 0, 0);
-        pacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[2], vf[kj][0], pacc, 0, 0, 0);
-        DP[qs][kj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[3], vf[kj][1], pacc, 0, 0, 0);
+        sacc = mfma16x16x32(f[0], kf[kj][0], sacc);
+        S[qs][kj] = mfma16x16x32(f[1], kf[kj][1], sacc);
+        pacc = mfma16x16x32(f[2], vf[kj][0], pacc);
+        DP[qs][kj] = mfma16x16x32(f[3], vf[kj][1], pacc);
       }
     };
     rd(ic<0>{});
@@ -1545,10 +1545,10 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_dq_kernel(AttnArgs a)
       for (int qi = 0; qi < 2; ++qi) {
         // dP^T accumulates onto -delta of this lane's query (one VALU op per score less)
         f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, pacc = {-dl[qi], -dl[qi], -dl[qi], -dl[qi]};
-        sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[0], qf[qi][0], sacc, 0, 0, 0);
-        sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[1], qf[qi][1], sacc, 0, 0, 0);
-        pacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[0], of[qi][0], pacc, 0, 0, 0);
-        pacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[1], of[qi][1], pacc, 0, 0, 0);
+        sacc = mfma16x16x32(kf[0], qf[qi][0], sacc);
+        sacc = mfma16x16x32(kf[1], qf[qi][1], sacc);
+        pacc = mfma16x16x32(vf[0], of[qi][0], pacc);
+        pacc = mfma16x16x32(vf[1], of[qi][1], pacc);
         if constexpr (kpart) {  // last, partial key tile only: padded keys get p = 0
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -1586,7 +1586,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attn_bwd_dq_kernel(AttnArgs a)
         const bf16x8 kf = cat_frag(kr[ks][2 * dt], kr[ks][2 * dt + 1]);
 #pragma unroll
         for (int qi = 0; qi < 2; ++qi)
-          dq[qi][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, pf[ks][qi], dq[qi][dt], 0, 0, 0);
+          dq[qi][dt] = mfma16x16x32(kf, pf[ks][qi], dq[qi][dt]);
       }
     }
     };

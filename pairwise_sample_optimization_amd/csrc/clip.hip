@@ -231,7 +231,7 @@ __global__ void resample_h_kernel(int H, int W, int OW, int y0, int rows, const 
         u = reinterpret_cast<const uint8_t*>(img)[e];
       } else {
         float t;
-        if (img_dtype == PSO_BF16) t = bf_round(bf_round(bf2f(reinterpret_cast<const bf16_t*>(img)[e]) + 1.0f) * 127.5f);
+        if (img_dtype == PSO_ELEM) t = bf_round(bf_round(bf2f(reinterpret_cast<const bf16_t*>(img)[e]) + 1.0f) * 127.5f);
         else t = (reinterpret_cast<const float*>(img)[e] + 1.0f) * 127.5f;
         u = (int)fminf(fmaxf(t, 0.f), 255.f);  // clamp, then .to(torch.uint8) truncates
       }
@@ -420,8 +420,9 @@ size_t pso_clip_preprocess_ws_bytes(int B, int H, int W, int size) {
 int pso_clip_preprocess(int B, int H, int W, const void* img, int img_dtype, int size, int patch, int kpad,
                         const float* mean, const float* stdv, void* out, void* ws, size_t ws_bytes, void* stream) {
   PSO_ARG_CHECK(B > 0 && H > 0 && W > 0 && img && out && ws && mean && stdv, "pso_clip_preprocess: null / bad shape");
-  PSO_ARG_CHECK(img_dtype == PSO_BF16 || img_dtype == PSO_F32 || img_dtype == PSO_U8,
-                "pso_clip_preprocess: the image must be bf16 / f32 in [-1, 1] or uint8, NHWC [B,H,W,3]");
+  // code 2 is uint8 here (PSO_U8), in both libraries: the f16 library therefore takes f32 and uint8 images only, and
+  // the other codes get the message that names the library to load
+  if (img_dtype != PSO_U8) PSO_DTYPE_CHECK(img_dtype, "pso_clip_preprocess (image: 16-bit / f32 in [-1, 1] or uint8)");
   PSO_ARG_CHECK(patch > 0 && size % patch == 0 && kpad >= 3 * patch * patch && kpad % 8 == 0,
                 "pso_clip_preprocess: size must be a multiple of patch, kpad >= 3 * patch^2 (multiple of 8)");
   PSO_ARG_CHECK(ws_bytes >= pso_clip_preprocess_ws_bytes(B, H, W, size), "pso_clip_preprocess: workspace too small");

@@ -9,21 +9,58 @@
 #include "../../include/pso_amd_knobs.h"
 #endif
 
-typedef uint16_t bf16_t;  // raw bf16 storage
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+// ---- the 16-bit element type: bf16 (default) or IEEE fp16 (-DPSO_ELEM_F16, libpso_amd_f16.so) ----
+// One compile-time switch for storage, MFMA operand vectors, conversions and the dtype code.  The names keep their
+// "bf" spelling under either type: bf16_t / bf2f / f2bf / pack2bf mean "the library's 16-bit element".  fp16
+// conversions are IEEE round-to-nearest-even: overflow gives +-inf (as torch's .half()), subnormals are kept.
+typedef uint16_t bf16_t;  // raw 16-bit element storage
+#ifdef PSO_ELEM_F16
+typedef _Float16 elem_native_t;
+#define PSO_ELEM PSO_F16
+#define PSO_ELEM_NAME "fp16"
+#define PSO_ELEM_ONES2 0x3C003C00u  // two elements holding 1.0
+#define PSO_MFMA_ASM "v_mfma_f32_16x16x32_f16"
+#else
+typedef __bf16 elem_native_t;
+#define PSO_ELEM PSO_BF16
+#define PSO_ELEM_NAME "bf16"
+#define PSO_ELEM_ONES2 0x3F803F80u
+#define PSO_MFMA_ASM "v_mfma_f32_16x16x32_bf16"
+#endif
+typedef __attribute__((ext_vector_type(8))) elem_native_t bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((ext_vector_type(2))) float f32x2_t;
+typedef __attribute__((ext_vector_type(2))) elem_native_t bf16x2_t;
 
+#ifdef PSO_ELEM_F16
+__device__ __forceinline__ float bf2f(bf16_t u) { return (float)__builtin_bit_cast(_Float16, u); }  // v_cvt_f32_f16
+#else
 __device__ __forceinline__ float bf2f(bf16_t u) { return __uint_as_float(((uint32_t)u) << 16); }
+#endif
 __device__ __forceinline__ bf16_t f2bf(float f) {
-  __bf16 b = (__bf16)f;  // v_cvt_pk_bf16_f32, RNE, NaN-preserving
+  elem_native_t b = (elem_native_t)f;  // v_cvt_pk_bf16_f32 / v_cvt_f16_f32: RNE, NaN-preserving
   return __builtin_bit_cast(bf16_t, b);
 }
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 __device__ __forceinline__ uint32_t pack2bf(float lo, float hi) {
-  // one v_cvt_pk_bf16_f32 (RNE, NaN-preserving) for both halves
+  // one v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32 (RNE, NaN-preserving) for both halves
   return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t{lo, hi}), bf16x2_t));
+}
+// the one matrix instruction of the library: D = A[16x32] . B[32x16] + C on 16-bit elements, fp32 accumulate
+__device__ __forceinline__ f32x4 mfma16x16x32(bf16x8 a, bf16x8 b, f32x4 acc) {
+#ifdef PSO_ELEM_F16
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc, 0, 0, 0);
+#else
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+#endif
+}
+// acc + a.lo * b.lo + a.hi * b.hi on packed element pairs (v_dot2c_f32_bf16 / v_dot2c_f32_f16)
+__device__ __forceinline__ float dot2_elem(uint32_t a, uint32_t b, float acc) {
+#ifdef PSO_ELEM_F16
+  return __builtin_amdgcn_fdot2(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), acc, false);
+#else
+  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), acc, false);
+#endif
 }
 // raw v_exp_f32 (2^x; results below 2^-126 flush to 0 -- fine for softmax weights, saves the denormal range fix-up)
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
@@ -76,6 +113,13 @@ void pso_note_kernel(const char* fmt, ...);
 // ---- error plumbing (host) ----
 void pso_set_error(const char* fmt, ...);
 int pso_check_launch(const char* what);
+// true for PSO_F32 and this library's own 16-bit code; otherwise sets the error (naming the library to load for the
+// other 16-bit type) and returns false
+bool pso_dtype_ok(int code, const char* who);
+#define PSO_DTYPE_CHECK(code, who)                  \
+  do {                                              \
+    if (!pso_dtype_ok((code), (who))) return PSO_ERR_ARG; \
+  } while (0)
 
 #define PSO_ARG_CHECK(cond, ...)            \
   do {                                      \

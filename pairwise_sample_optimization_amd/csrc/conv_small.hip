@@ -14,8 +14,6 @@
 #define CS_CH 64         // channels per chunk
 #define CS_PITCH 72      // bf16 per staged pixel (64 + 8: 144-B pitch)
 
-typedef __attribute__((ext_vector_type(2))) __bf16 cs_bf16x2;
-
 // CIN > 0: the channel count as a constant (the weight offsets become scalar-load immediates: no per-load SGPR
 // address arithmetic); 0: read from the argument
 template <int COUT, int CIN>
@@ -59,8 +57,7 @@ __global__ __launch_bounds__(256) void conv3x3_smallc_kernel(int H, int W, int c
           const uint32_t* wp = w32 + c * wrow + (tap * Cin + c0 + piece * 8) / 2;  // wave-uniform
 #pragma unroll
           for (int k = 0; k < 4; ++k)
-            acc[c] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(cs_bf16x2, xv[k]),
-                                                     __builtin_bit_cast(cs_bf16x2, wp[k]), acc[c], false);
+            acc[c] = dot2_elem(xv[k], wp[k], acc[c]);
         }
       }
     }

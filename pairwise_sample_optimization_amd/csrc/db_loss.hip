@@ -23,7 +23,7 @@
 #define DB_THREADS 256
 
 __device__ __forceinline__ void db_load4(const void* p, int dtype, size_t i, float* e) {
-  if (dtype == PSO_BF16) {
+  if (dtype == PSO_ELEM) {
     const uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(p) + i);
     e[0] = bf2f(v.x & 0xffff); e[1] = bf2f(v.x >> 16); e[2] = bf2f(v.y & 0xffff); e[3] = bf2f(v.y >> 16);
   } else {
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(DB_THREADS) void db_grad_kernel(int B, int n, int n
     float o[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = scale * ((e[j] * -s + ns[j]) - ts[j]);
-    if (deps_dtype == PSO_BF16)
+    if (deps_dtype == PSO_ELEM)
       *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(deps) + base + i) =
           make_uint2(pack2bf(o[0], o[1]), pack2bf(o[2], o[3]));
     else
@@ -187,7 +187,7 @@ int pso_db_loss_fwd(int loss_type, int B, int n, const void* eps, const void* ep
   PSO_ARG_CHECK(B > 0 && B <= 1024 && n > 0 && (n % 4) == 0, "pso_db_loss_fwd: need 0<B<=1024, n%%4==0");
   PSO_ARG_CHECK(eps && noisy && x0 && sigma && loss_out, "pso_db_loss_fwd: null pointer");
   PSO_ARG_CHECK(loss_type == PSO_DB_HINGE || eps_ref, "pso_db_loss_fwd: loss 'pso' needs the reference eps");
-  PSO_ARG_CHECK(eps_dtype == PSO_F32 || eps_dtype == PSO_BF16, "pso_db_loss_fwd: bad eps dtype");
+  PSO_DTYPE_CHECK(eps_dtype, "pso_db_loss_fwd");
   PSO_ARG_CHECK(ws && ws_bytes >= pso_db_loss_ws_bytes(B, n), "pso_db_loss_fwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int nchunks = cdiv(n, DB_CHUNK);
@@ -206,8 +206,8 @@ int pso_db_loss_bwd(int loss_type, int B, int n, const void* eps, int eps_dtype,
   PSO_ARG_CHECK(loss_type == PSO_DB_SIGMOID || loss_type == PSO_DB_HINGE, "pso_db_loss_bwd: bad loss type");
   PSO_ARG_CHECK(B > 0 && B <= 1024 && n > 0 && (n % 4) == 0, "pso_db_loss_bwd: need 0<B<=1024, n%%4==0");
   PSO_ARG_CHECK(eps && noisy && x0 && sigma && deps, "pso_db_loss_bwd: null pointer");
-  PSO_ARG_CHECK(eps_dtype == PSO_F32 || eps_dtype == PSO_BF16, "pso_db_loss_bwd: bad eps dtype");
-  PSO_ARG_CHECK(deps_dtype == PSO_F32 || deps_dtype == PSO_BF16, "pso_db_loss_bwd: bad deps dtype");
+  PSO_DTYPE_CHECK(eps_dtype, "pso_db_loss_bwd");
+  PSO_DTYPE_CHECK(deps_dtype, "pso_db_loss_bwd");
   PSO_ARG_CHECK(ws && ws_bytes >= pso_db_loss_ws_bytes(B, n), "pso_db_loss_bwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int nchunks = cdiv(n, DB_CHUNK);

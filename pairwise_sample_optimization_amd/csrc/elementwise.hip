@@ -234,10 +234,15 @@ __global__ void cast_bf16_f32_kernel(long n, const bf16_t* __restrict__ x, float
     done = n & ~7L;
     GRID_STRIDE(v, n >> 3) {
       const uint4 u = reinterpret_cast<const uint4*>(x)[v];
+#ifdef PSO_ELEM_F16
+      reinterpret_cast<float4*>(y)[2 * v] = make_float4(bf2f(u.x & 0xffff), bf2f(u.x >> 16), bf2f(u.y & 0xffff), bf2f(u.y >> 16));
+      reinterpret_cast<float4*>(y)[2 * v + 1] = make_float4(bf2f(u.z & 0xffff), bf2f(u.z >> 16), bf2f(u.w & 0xffff), bf2f(u.w >> 16));
+#else  // bf16 -> f32 is a shift: the high element needs only its mask
       reinterpret_cast<float4*>(y)[2 * v] = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u),
                                                         __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
       reinterpret_cast<float4*>(y)[2 * v + 1] = make_float4(__uint_as_float(u.z << 16), __uint_as_float(u.z & 0xffff0000u),
                                                             __uint_as_float(u.w << 16), __uint_as_float(u.w & 0xffff0000u));
+#endif
     }
   }
   GRID_STRIDE(i, n - done) y[done + i] = bf2f(x[done + i]);
@@ -434,14 +439,16 @@ int pso_gather_rows(long n, long row_bytes, const void* src, const int64_t* idx,
 
 int pso_nchw_to_nhwc(int B, int C, int Cp, long HW, const void* src, int src_dtype, float scale, void* dst,
                      void* stream) {
-  PSO_ARG_CHECK(src && dst && Cp >= C && (src_dtype == PSO_F32 || src_dtype == PSO_BF16), "pso_nchw_to_nhwc: bad args");
+  PSO_DTYPE_CHECK(src_dtype, "pso_nchw_to_nhwc");
+  PSO_ARG_CHECK(src && dst && Cp >= C, "pso_nchw_to_nhwc: bad args");
   nchw_to_nhwc_kernel<<<grid_for((long)B * Cp * HW), 256, 0, (hipStream_t)stream>>>(
       B, C, Cp, HW, src, src_dtype == PSO_F32, scale, (bf16_t*)dst);
   return pso_check_launch("pso_nchw_to_nhwc");
 }
 
 int pso_nhwc_to_nchw(int B, int C, long HW, const void* src, void* dst, int dst_dtype, void* stream) {
-  PSO_ARG_CHECK(src && dst && (dst_dtype == PSO_F32 || dst_dtype == PSO_BF16), "pso_nhwc_to_nchw: bad args");
+  PSO_DTYPE_CHECK(dst_dtype, "pso_nhwc_to_nchw");
+  PSO_ARG_CHECK(src && dst, "pso_nhwc_to_nchw: bad args");
   nhwc_to_nchw_kernel<<<grid_for((long)B * C * HW), 256, 0, (hipStream_t)stream>>>(B, C, HW, (const bf16_t*)src,
                                                                                   dst, dst_dtype == PSO_F32);
   return pso_check_launch("pso_nhwc_to_nchw");

@@ -391,7 +391,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_bf16_kernel(GemmArgs g) 
 #pragma unroll
       for (int i = 0; i < MI; ++i)
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
+        for (int j = 0; j < NJ; ++j) acc[i][j] = mfma16x16x32(fb[j], fa[i], acc[i][j]);
       __builtin_amdgcn_s_setprio(0);
     };
     if (nt > 0) issue_tile(0, 0);
@@ -440,7 +440,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_bf16_kernel(GemmArgs g) 
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
+      for (int j = 0; j < NJ; ++j) acc[i][j] = mfma16x16x32(bfr[j], af[i], acc[i][j]);
     __builtin_amdgcn_s_setprio(0);
   };
   // a LoRA K-tail of rank <= 32 fills only the first 32-deep half of its (last) K-tile, the rest being zero padding:
@@ -592,7 +592,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_bf16_kernel(GemmArgs g) 
     return;
   }
   if constexpr (EPI == EPI_NONE && !PIPE && BM * (BN + 8) * 2 <= STAGES * (BM + BN) * BK * 2) {
-    if (g.stage_epi && epi_fast && g.out_dtype == PSO_BF16 && !g.accumulate && nt > 0) {
+    if (g.stage_epi && epi_fast && g.out_dtype == PSO_ELEM && !g.accumulate && nt > 0) {
       // Staged epilogue: y = bf16(acc * alpha + bias [+ rowbias]) goes to LDS in the MFMA layout, then the workgroup
       // walks the tile in 16-B chunks: residual loaded and output stored as whole 16-B vectors (half the store
       // instructions of the 8-B per-lane layout).  The residual is added to the bf16-rounded projection, as the
@@ -683,7 +683,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_bf16_kernel(GemmArgs g) 
           v[0] += bf2f(eadd[i][j].x & 0xffff); v[1] += bf2f(eadd[i][j].x >> 16);
           v[2] += bf2f(eadd[i][j].y & 0xffff); v[3] += bf2f(eadd[i][j].y >> 16);
         }
-        if (g.out_dtype == PSO_BF16) {
+        if (g.out_dtype == PSO_ELEM) {
           *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(outp) + (long)m * g.ldo + n) =
               make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
         } else {
@@ -727,7 +727,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_bf16_kernel(GemmArgs g) 
           const uint2 rv = *reinterpret_cast<const uint2*>(g.resid + (long)m * g.ldr + n);
           v[0] += bf2f(rv.x & 0xffff); v[1] += bf2f(rv.x >> 16); v[2] += bf2f(rv.y & 0xffff); v[3] += bf2f(rv.y >> 16);
         }
-        if (g.out_dtype == PSO_BF16) {
+        if (g.out_dtype == PSO_ELEM) {
           *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(outp) + (long)m * g.ldo + n) =
               make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
         } else {
@@ -744,7 +744,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_bf16_kernel(GemmArgs g) 
           if (g.bias) x += bf2f(g.bias[n + r]);
           if (g.rowbias) x += bf2f(g.rowbias[(long)(m / g.rows_per_group) * g.ld_rowbias + n + r]);
           if (g.resid) x += bf2f(g.resid[(long)m * g.ldr + n + r]);
-          if (g.out_dtype == PSO_BF16) {
+          if (g.out_dtype == PSO_ELEM) {
             reinterpret_cast<bf16_t*>(outp)[(long)m * g.ldo + n + r] = f2bf(x);
           } else {
             float* o = reinterpret_cast<float*>(outp) + (long)m * g.ldo + n + r;
@@ -847,7 +847,7 @@ __global__ void gemm_splitk_reduce_kernel(GemmArgs g, int ks) {
     if (g.bias) v[r] += bf2f(g.bias[n + r]);
     if (g.rowbias) v[r] += bf2f(g.rowbias[(long)(m / g.rows_per_group) * g.ld_rowbias + n + r]);
   }
-  if (g.out_dtype == PSO_BF16) {
+  if (g.out_dtype == PSO_ELEM) {
     if (g.resid) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] = bf2f(f2bf(v[r])) + bf2f(g.resid[(long)m * g.ldr + n + r]);
@@ -933,7 +933,7 @@ static int run_gemm(GemmArgs& g, hipStream_t st) {
   }
   // staged 16-B epilogue for bf16 outputs with 16-B aligned rows (5-10 % on the K = 640 / 1280 projections with
   // bias + residual, tools/epi_bench.py); variant 41 keeps the per-lane 8-B epilogue (A/B knob)
-  g.stage_epi = gv_raw != 41 && g.out_dtype == PSO_BF16 && al16(g.out) && (g.ldo % 8) == 0 &&
+  g.stage_epi = gv_raw != 41 && g.out_dtype == PSO_ELEM && al16(g.out) && (g.ldo % 8) == 0 &&
                 (!g.resid || (al16(g.resid) && (g.ldr % 8) == 0));
   g.vec_ok = (g.ldo % 4) == 0 && (g.out_dtype == PSO_F32 ? al16(g.out) : al8(g.out)) &&
              (!g.resid || ((g.ldr % 4) == 0 && al8(g.resid))) && (!g.bias || al8(g.bias)) &&
@@ -983,7 +983,7 @@ static int run_gemm(GemmArgs& g, hipStream_t st) {
     const bool conv8 = cv.mode == PSO_CONV_NORMAL && cv.ks == 3 && cv.stride == 1 && cv.pad == 1 && cv.H == cv.Ho &&
                        cv.W == cv.Wo && cv.C2 == 0 && (cv.C1 % 64) == 0 && cv.C1 <= 4096 && (hw % 256) == 0 &&
                        (cv.H & (cv.H - 1)) == 0 && (cv.W & (cv.W - 1)) == 0 && cv.W >= 8 &&
-                       (g.N % 320) == 0 && !g.a2 && g.out_dtype == PSO_BF16 && !g.accumulate && al16(g.out) &&
+                       (g.N % 320) == 0 && !g.a2 && g.out_dtype == PSO_ELEM && !g.accumulate && al16(g.out) &&
                        (g.ldo % 8) == 0 && (!g.resid || (al16(g.resid) && (g.ldr % 8) == 0)) &&
                        (!g.bias || al8(g.bias)) && (!g.rowbias || (al8(g.rowbias) && g.rows_per_group == hw)) &&
                        fits30((long)g.M + 2L * (cv.W + 1), cv.C1) && fits30(g.N, g.ldb1) && al16(g.a1) && al16(g.b1);
@@ -997,7 +997,7 @@ static int run_gemm(GemmArgs& g, hipStream_t st) {
   // epilogue, LoRA K-tail, bias / alpha / residual.  Default for N >= 2560 with >= 256 tiles (tools/gemm8_ab.py, one
   // box: q/k/v 16384 x 3840 x 1280 1071 vs 937 TF/s, ff.out dX 8192 x 5120 x 1280 991 vs 945); N = 1280 keeps 128x160
   // (1.25 rounds of 256x256 tiles at M = 16384: 805 vs 928).  Variant 30 forces it, 31 keeps it off everywhere.
-  const bool base8 = !g.conv.mode && !g.rowbias && g.out_dtype == PSO_BF16 && !g.accumulate && (g.K1 % 64) == 0 &&
+  const bool base8 = !g.conv.mode && !g.rowbias && g.out_dtype == PSO_ELEM && !g.accumulate && (g.K1 % 64) == 0 &&
                      al16(g.a1) && al16(g.b1) && (g.lda1 % 8) == 0 && (g.ldb1 % 8) == 0 && al16(g.out) &&
                      (g.ldo % 8) == 0 && (!g.resid || (al16(g.resid) && (g.ldr % 8) == 0)) &&
                      (!g.bias || al8(g.bias)) && fits30(g.M, g.lda1) && fits30(g.N, g.ldb1) &&
@@ -1219,7 +1219,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(int M, int I, int J, co
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[b], af[a], acc[a][b], 0, 0, 0);
+        for (int b = 0; b < 2; ++b) acc[a][b] = mfma16x16x32(bfr[b], af[a], acc[a][b]);
     }
     if (t + 1 < t_end) store(cur ^ 1);
     __syncthreads();
@@ -1333,7 +1333,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn128_kernel(int M, int I, int J,
 #pragma unroll
       for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[b], af[a], acc[a][b], 0, 0, 0);
+        for (int b = 0; b < 4; ++b) acc[a][b] = mfma16x16x32(bfr[b], af[a], acc[a][b]);
       __builtin_amdgcn_s_setprio(0);
     }
     // the next stage landed (every wave's pieces), and every wave's reads of this stage retired before it is restaged
@@ -1471,7 +1471,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tn256_kernel(int M, int I, int J,
 #pragma unroll
       for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[b], af[a], acc[a][b], 0, 0, 0);
+        for (int b = 0; b < 8; ++b) acc[a][b] = mfma16x16x32(bfr[b], af[a], acc[a][b]);
       __builtin_amdgcn_s_setprio(0);
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -1664,7 +1664,7 @@ int pso_gemm(int M, int N, const void* a1, long lda1, int K1, const void* b1, lo
   PSO_ARG_CHECK(al16(a1) && al16(b1) && (lda1 % 8) == 0 && (ldb1 % 8) == 0, "pso_gemm: A1/B1 must be 16-B aligned rows");
   PSO_ARG_CHECK(!a2 || (b2 && (K2 % 8) == 0 && al16(a2) && al16(b2) && (lda2 % 8) == 0 && (ldb2 % 8) == 0),
                 "pso_gemm: bad second operand");
-  PSO_ARG_CHECK(out_dtype == PSO_BF16 || out_dtype == PSO_F32, "pso_gemm: bad out dtype");
+  PSO_DTYPE_CHECK(out_dtype, "pso_gemm");
   PSO_ARG_CHECK((long)M * lda1 < 0x7fffffffL && (long)N * ldb1 < 0x7fffffffL,
                 "pso_gemm: operand spans more than 2^31 elements");
   PSO_ARG_CHECK(!accumulate || out_dtype == PSO_F32, "pso_gemm: accumulate needs f32 output");
@@ -1699,7 +1699,7 @@ int pso_gemm_ws(int M, int N, const void* a1, long lda1, int K1, const void* b1,
   PSO_ARG_CHECK(al16(a1) && al16(b1) && (lda1 % 8) == 0 && (ldb1 % 8) == 0, "pso_gemm_ws: A1/B1 must be 16-B aligned rows");
   PSO_ARG_CHECK(!a2 || (b2 && (K2 % 8) == 0 && al16(a2) && al16(b2) && (lda2 % 8) == 0 && (ldb2 % 8) == 0),
                 "pso_gemm_ws: bad second operand");
-  PSO_ARG_CHECK(out_dtype == PSO_BF16 || out_dtype == PSO_F32, "pso_gemm_ws: bad out dtype");
+  PSO_DTYPE_CHECK(out_dtype, "pso_gemm_ws");
   PSO_ARG_CHECK((long)M * lda1 < 0x7fffffffL && (long)N * ldb1 < 0x7fffffffL,
                 "pso_gemm_ws: operand spans more than 2^31 elements");
   PSO_ARG_CHECK(!accumulate || out_dtype == PSO_F32, "pso_gemm_ws: accumulate needs f32 output");
@@ -1732,7 +1732,7 @@ int pso_gemm_batched(int batch, int M, int N, int K, const void* a, long lda, lo
   PSO_ARG_CHECK(a && b && out, "pso_gemm_batched: null operand");
   PSO_ARG_CHECK(al16(a) && al16(b) && (lda % 8) == 0 && (ldb % 8) == 0 && (stride_a % 8) == 0 && (stride_b % 8) == 0,
                 "pso_gemm_batched: A/B need 16-B aligned rows and batch strides");
-  PSO_ARG_CHECK(out_dtype == PSO_BF16 || out_dtype == PSO_F32, "pso_gemm_batched: bad out dtype");
+  PSO_DTYPE_CHECK(out_dtype, "pso_gemm_batched");
   PSO_ARG_CHECK((long)M * lda < 0x7fffffffL && (long)N * ldb < 0x7fffffffL,
                 "pso_gemm_batched: one operand spans more than 2^31 elements");
   GemmArgs g{};
@@ -1757,11 +1757,12 @@ int pso_conv2d(int mode, int B, const void* src1, int C1, const void* src2, int 
   PSO_ARG_CHECK(ks == 1 || ks == 3, "pso_conv2d: ks must be 1 or 3");
   PSO_ARG_CHECK(mode != PSO_CONV_UP2 || (Ho == 2 * H && Wo == 2 * W && stride == 1), "pso_conv2d: UP2 geometry");
   PSO_ARG_CHECK(!a2 || ((K2 % 8) == 0 && b2 && al16(a2) && al16(b2)), "pso_conv2d: bad second operand");
+  PSO_DTYPE_CHECK(out_dtype, "pso_conv2d");
   PSO_ARG_CHECK(!accumulate || out_dtype == PSO_F32, "pso_conv2d: accumulate needs f32 output");
   // Cout <= 3 (the VAE decoder's conv_out to RGB): a direct convolution instead of an N = 3 GEMM padded to 64-column
   // MFMA tiles (conv_small.hip; 1024^2: 1.34 ms -> see DESIGN §4 / profiles/r06_vae_conv_out_ab.log)
   if (mode == PSO_CONV_NORMAL && ks == 3 && stride == 1 && pad == 1 && Ho == H && Wo == W && C2 == 0 && !a2 &&
-      !rowbias && !resid && alpha == 1.f && out_dtype == PSO_BF16 && !accumulate && ldo == Cout && Cout <= 3 &&
+      !rowbias && !resid && alpha == 1.f && out_dtype == PSO_ELEM && !accumulate && ldo == Cout && Cout <= 3 &&
       pso_conv3x3_smallc_run(B, H, W, C1, Cout, src1, weight, bias, out, (hipStream_t)stream) == PSO_OK)
     return PSO_OK;
   GemmArgs g{};
@@ -1802,6 +1803,7 @@ int pso_conv2d_ws(int mode, int B, const void* src1, int C1, const void* src2, i
   PSO_ARG_CHECK(ks == 1 || ks == 3, "pso_conv2d_ws: ks must be 1 or 3");
   PSO_ARG_CHECK(mode != PSO_CONV_UP2 || (Ho == 2 * H && Wo == 2 * W && stride == 1), "pso_conv2d_ws: UP2 geometry");
   PSO_ARG_CHECK(!a2 || ((K2 % 8) == 0 && b2 && al16(a2) && al16(b2)), "pso_conv2d_ws: bad second operand");
+  PSO_DTYPE_CHECK(out_dtype, "pso_conv2d_ws");
   PSO_ARG_CHECK(!accumulate || out_dtype == PSO_F32, "pso_conv2d_ws: accumulate needs f32 output");
   GemmArgs g{};
   const int Ct = C1 + C2;
@@ -1841,7 +1843,7 @@ int pso_gemm_geglu(int M, int N, const void* a, long lda, int K, const void* w, 
   g.b1 = (const bf16_t*)w; g.ldb1 = ldw;
   g.M = M; g.N = N; g.alpha = 1.f;
   g.bias = (const bf16_t*)bias;
-  g.out = out; g.ldo = ldo; g.out_dtype = PSO_BF16;
+  g.out = out; g.ldo = ldo; g.out_dtype = PSO_ELEM;
   g.out2 = out_pre; g.ldo2 = ld_pre;
   g.tail_m = (pre_rows > 0 && pre_rows < M) ? pre_rows : M;
   g.vec_ok = 1; g.rows_per_group = 1;
@@ -1884,7 +1886,7 @@ int pso_gemm_geglu_bwd(int M, int N, const void* a, long lda, int K, const void*
   g.a1 = (const bf16_t*)a; g.lda1 = lda; g.K1 = K;
   g.b1 = (const bf16_t*)w; g.ldb1 = ldw;
   g.M = M; g.N = N; g.alpha = 1.f;
-  g.out = out; g.ldo = ldo; g.out_dtype = PSO_BF16;
+  g.out = out; g.ldo = ldo; g.out_dtype = PSO_ELEM;
   g.aux = (const bf16_t*)pre; g.ldaux = ld_pre;
   g.vec_ok = 1; g.rows_per_group = 1;
   g.group_m = g_gemm_group > 0 ? g_gemm_group : PSO_GEMM_GROUP_M;

@@ -424,11 +424,11 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(Gemm8Args g) {
 #pragma unroll
           for (int j = 0; j < (hb ? NJ1 : NJ0); ++j) {
             if constexpr (BN == 320)  // accumulator tied in place (the builtin form double-buffers and spills here)
-              asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc[ha][hb][i][j]) : "v"(bfr[j][kk]),
+              asm volatile(PSO_MFMA_ASM " %0, %1, %2, %0" : "+v"(acc[ha][hb][i][j]) : "v"(bfr[j][kk]),
                            "v"(af[i][kk]));
             else
               acc[ha][hb][i][j] =
-                  __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j][kk], af[i][kk], acc[ha][hb][i][j], 0, 0, 0);
+                  mfma16x16x32(bfr[j][kk], af[i][kk], acc[ha][hb][i][j]);
           }
       if constexpr (BN == 320)  // the asm MFMAs are invisible to the hazard recognizer: see the FP8 form's note
         asm volatile("s_nop 7"
@@ -526,7 +526,7 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(Gemm8Args g) {
             for (int i = 0; i < MI; ++i)
 #pragma unroll
               for (int j = 0; j < NJ; ++j)
-                asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc[ha][hb][i][j]) : "v"(tw2[hb][j]),
+                asm volatile(PSO_MFMA_ASM " %0, %1, %2, %0" : "+v"(acc[ha][hb][i][j]) : "v"(tw2[hb][j]),
                              "v"(ta2[ha][i]));
       }
     }

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(64 * SK_W) void gemm_skinny_nt_kernel(int M, int N,
       for (int t = 0; t < SK_MT; ++t)
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
-          acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[u][j], af[u][t], acc[t][j], 0, 0, 0);
+          acc[t][j] = mfma16x16x32(bfr[u][j], af[u][t], acc[t][j]);
   }
   // reduce the eight K-partials through LDS, one 16-row tile at a time
   // fragment position (j, l) of tile t holds out[r0 + 16t + (l & 15)][j*16 + (l >> 4)*4 .. +3]

@@ -187,9 +187,9 @@ __global__ __launch_bounds__(256, NJT == 6 ? 1 : 2) void gemm_tn_rank_kernel(Tnr
 #pragma unroll
         for (int j = 0; j < NJT; ++j) {
           if (OUT_JC)  // lane holds D^T[j = 16j' + 4g + r][c = 16ci + cl]: consecutive lanes -> consecutive c
-            acc[ci][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(uf[j], xf[ci], acc[ci][j], 0, 0, 0);
+            acc[ci][j] = mfma16x16x32(uf[j], xf[ci], acc[ci][j]);
           else  // lane holds D[c = 16ci + 4g + r][j = 16j' + cl]
-            acc[ci][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[ci], uf[j], acc[ci][j], 0, 0, 0);
+            acc[ci][j] = mfma16x16x32(xf[ci], uf[j], acc[ci][j]);
         }
     }
   }

@@ -16,10 +16,15 @@
 
 // DMD2 replay modes (PSO_MODE_DMD_F16 / _BF16): every intermediate of the reference's latent-dtype arithmetic is
 // rounded to that dtype (torch's CPU/GPU fp16 and bf16 element-wise ops compute in fp32 and round the result).
+// The latent dtype of a replay mode is the caller's choice, not the library's element type: both roundings are
+// spelled with their literal types (bf_round would follow -DPSO_ELEM_F16).
+__device__ __forceinline__ float round_bf16(float x) {
+  return __uint_as_float((uint32_t)__builtin_bit_cast(uint16_t, (__bf16)x) << 16);
+}
 template <int MODE>
 __device__ __forceinline__ float rl(float x) {
   if constexpr (MODE == PSO_MODE_DMD_F16) return (float)(_Float16)x;
-  else if constexpr (MODE == PSO_MODE_DMD_BF16) return bf_round(x);
+  else if constexpr (MODE == PSO_MODE_DMD_BF16) return round_bf16(x);
   else return x;
 }
 // An opaque copy: the compiler cannot fuse an operation across it.  Every product / quotient of the step arithmetic
@@ -81,7 +86,7 @@ __device__ __forceinline__ float step_dmu_deps(const Coef& k) {
 }
 
 __device__ __forceinline__ void load4_eps(const void* eps, int dtype, size_t i, float* e) {
-  if (dtype == PSO_BF16) {
+  if (dtype == PSO_ELEM) {
     const uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(eps) + i);
     e[0] = bf2f(v.x & 0xffff); e[1] = bf2f(v.x >> 16); e[2] = bf2f(v.y & 0xffff); e[3] = bf2f(v.y >> 16);
   } else {
@@ -258,7 +263,7 @@ __global__ __launch_bounds__(LP_THREADS) void pair_grad_kernel(
     float o[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = scale * (ps[j] - step_mean<MODE>(xs[j], e[j], k));
-    if (deps_dtype == PSO_BF16) {
+    if (deps_dtype == PSO_ELEM) {
       *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(deps) + base + i) =
           make_uint2(pack2bf(o[0], o[1]), pack2bf(o[2], o[3]));
     } else {
@@ -310,7 +315,7 @@ int pso_step_logprob(int mode, int B, int n, const float* sample, const void* ep
   PSO_ARG_CHECK(B > 0 && n > 0 && (n % 4) == 0, "pso_step_logprob: need B>0, n>0, n%%4==0 (B=%d n=%d)", B, n);
   PSO_ARG_CHECK(sample && eps && coef && log_prob, "pso_step_logprob: null pointer");
   PSO_ARG_CHECK(prev_in || (noise && prev_out), "pso_step_logprob: need prev_in, or noise and prev_out");
-  PSO_ARG_CHECK(eps_dtype == PSO_F32 || eps_dtype == PSO_BF16, "pso_step_logprob: bad eps dtype");
+  PSO_DTYPE_CHECK(eps_dtype, "pso_step_logprob");
   PSO_ARG_CHECK(ws && ws_bytes >= pso_step_logprob_ws_bytes(B, n), "pso_step_logprob: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int nchunks = cdiv(n, LP_CHUNK);
@@ -331,7 +336,7 @@ int pso_pair_loss_fwd(int mode, int P, int n, const float* x, const float* x_pre
                 "pso_pair_loss_fwd: need 0<P<=1024, n>0, n%%4==0 (P=%d n=%d)", P, n);
   PSO_ARG_CHECK(x && x_prev && eps_pol && eps_ref && coef && pref && lp_out && loss_out,
                 "pso_pair_loss_fwd: null pointer");
-  PSO_ARG_CHECK(eps_dtype == PSO_F32 || eps_dtype == PSO_BF16, "pso_pair_loss_fwd: bad eps dtype");
+  PSO_DTYPE_CHECK(eps_dtype, "pso_pair_loss_fwd");
   PSO_ARG_CHECK(ws && ws_bytes >= pso_pair_loss_ws_bytes(P, n), "pso_pair_loss_fwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int nchunks = cdiv(n, LP_CHUNK);
@@ -350,8 +355,8 @@ int pso_pair_loss_bwd(int mode, int P, int n, const float* x, const float* x_pre
   PSO_ARG_CHECK(PSO_MODE_OK(mode), "pso_pair_loss_bwd: bad mode %d", mode);
   PSO_ARG_CHECK(P > 0 && n > 0 && (n % 4) == 0, "pso_pair_loss_bwd: need P>0, n>0, n%%4==0");
   PSO_ARG_CHECK(x && x_prev && eps_pol && coef && pref && deps_pol, "pso_pair_loss_bwd: null pointer");
-  PSO_ARG_CHECK(eps_dtype == PSO_F32 || eps_dtype == PSO_BF16, "pso_pair_loss_bwd: bad eps dtype");
-  PSO_ARG_CHECK(deps_dtype == PSO_F32 || deps_dtype == PSO_BF16, "pso_pair_loss_bwd: bad deps dtype");
+  PSO_DTYPE_CHECK(eps_dtype, "pso_pair_loss_bwd");
+  PSO_DTYPE_CHECK(deps_dtype, "pso_pair_loss_bwd");
   PSO_ARG_CHECK(ws && ws_bytes >= pso_pair_loss_ws_bytes(P, n), "pso_pair_loss_bwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int nchunks = cdiv(n, LP_CHUNK);

@@ -18,6 +18,7 @@ eps (adapters disabled, DB:1894-1920) comes from the same paired UNet pass as th
 
 import torch
 
+from . import _lib
 from . import kernels as K
 from .schedulers import EulerDiscreteScheduler, db_distill_timesteps
 from .trainer import lora_optimizer_step
@@ -31,6 +32,8 @@ class DreamBoothPSOTrainer:
         """Defaults: DB argparse defaults (DB:636-674, 757-777) overridden by the recipe scripts/pso_dog.sh."""
         if loss_type not in ("pso", "pso_db"):
             raise ValueError(f"Unknown loss type {loss_type}")  # DB:1929
+        # this trainer has no loss scaler: under the f16 library it would train fp16 without one
+        _lib.require_bf16("DreamBooth PSO training (DreamBoothPSOTrainer)")
         self.unet, self.vae = unet, vae
         self.loss_type = loss_type
         self.lt = K.DB_SIGMOID if loss_type == "pso" else K.DB_HINGE

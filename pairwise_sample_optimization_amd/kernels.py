@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import check, lib, ptr, require_cuda, stream_ptr, dtype_code, PSO_BF16, PSO_F32
 
 CONV_NORMAL, CONV_UP2, CONV_T2 = 1, 2, 3
-BF16 = torch.bfloat16
+ELEM = _lib.ELEM_DTYPE  # the loaded library's 16-bit element type: bf16, or fp16 under PSO_LIB=f16
 
 # Optional per-launch accounting of the MFMA GEMM/conv kernel (bench.py roofline): list of (flops, ev0, ev1)
 PROFILE = None
@@ -103,14 +103,14 @@ def gemm_set_variant(v):
 
 
 def gemm(a, w, *, bias=None, resid=None, a2=None, w2=None, alpha=1.0, rowbias=None, rows_per_group=1, out=None,
-         out_dtype=BF16, accumulate=False, tail_group_n=0, tail_rows=0):
+         out_dtype=ELEM, accumulate=False, tail_group_n=0, tail_rows=0):
     """out[M,N] = alpha*(a @ w^T + a2 @ w2^T) + bias + rowbias[m // rows_per_group] + resid.
     tail_group_n > 0: output column group j uses a2[:, j*K2:(j+1)*K2] with w2 [N, K2].
     tail_rows > 0: only the first tail_rows rows take the a2 term (a2 has tail_rows rows)."""
     require_cuda(a, w)
     M, K1 = a.shape
     N = w.shape[0]
-    assert w.shape[1] == K1 and a.dtype == BF16 and w.dtype == BF16
+    assert w.shape[1] == K1 and a.dtype == ELEM and w.dtype == ELEM
     K2 = 0
     if a2 is not None:
         K2 = w2.shape[1]
@@ -140,12 +140,12 @@ def gemm(a, w, *, bias=None, resid=None, a2=None, w2=None, alpha=1.0, rowbias=No
     return out
 
 
-def gemm_batched(a, w, alpha=1.0, out=None, out_dtype=BF16):
+def gemm_batched(a, w, alpha=1.0, out=None, out_dtype=ELEM):
     """out[z] = alpha * a[z] @ w[z]^T for a [Z, M, K], w [Z, N, K] (bf16, rows contiguous) -> [Z, M, N]."""
     require_cuda(a, w)
     Z, M, Kd = a.shape
     N = w.shape[1]
-    assert w.shape[0] == Z and w.shape[2] == Kd and a.dtype == BF16 and w.dtype == BF16
+    assert w.shape[0] == Z and w.shape[2] == Kd and a.dtype == ELEM and w.dtype == ELEM
     assert a.stride(2) == 1 and w.stride(2) == 1
     if out is None:
         out = torch.empty((Z, M, N), device=a.device, dtype=out_dtype)
@@ -166,7 +166,7 @@ def gemm_grouped_skinny(a, w, groups, out=None, alpha=1.0):
     Kg = KG // groups
     assert w.shape[1] == KG and KG == Kg * groups
     if out is None:
-        out = torch.empty((M, groups * N), device=a.device, dtype=BF16)
+        out = torch.empty((M, groups * N), device=a.device, dtype=ELEM)
     e0 = _prof_begin()
     check(lib().pso_gemm_skinny_grouped(M, N, Kg, ptr(a), _row_stride(a), ptr(w), _row_stride(w), float(alpha),
                                         ptr(out), _row_stride(out), int(groups), stream_ptr()), "pso_gemm_skinny_grouped")
@@ -195,7 +195,7 @@ def gemm_geglu(a, w_int, b_int, out_pre=None, out=None, pre_rows=0):
     M, Kd = a.shape
     N = w_int.shape[0]
     if out is None:
-        out = torch.empty((M, N // 2), device=a.device, dtype=BF16)
+        out = torch.empty((M, N // 2), device=a.device, dtype=ELEM)
     e0 = _prof_begin()
     check(lib().pso_gemm_geglu(M, N, ptr(a), _row_stride(a), Kd, ptr(w_int), _row_stride(w_int), ptr(b_int),
                                ptr(out), _row_stride(out), ptr(out_pre),
@@ -212,7 +212,7 @@ def gemm_geglu_bwd(a, w, pre, out=None):
     M, Kd = a.shape
     N = w.shape[0]
     if out is None:
-        out = torch.empty((M, 2 * N), device=a.device, dtype=BF16)
+        out = torch.empty((M, 2 * N), device=a.device, dtype=ELEM)
     e0 = _prof_begin()
     check(lib().pso_gemm_geglu_bwd(M, N, ptr(a), _row_stride(a), Kd, ptr(w), _row_stride(w), ptr(pre),
                                    _row_stride(pre), ptr(out), _row_stride(out), stream_ptr()), "pso_gemm_geglu_bwd")
@@ -224,7 +224,7 @@ def quant_rows_fp8(x, q=None, e=None):
     """Row-wise OCP e4m3 quantisation with a power-of-two scale per row: returns (q uint8 [M, K], e uint8 [M]) with
     x[m] ~= e4m3(q[m]) * 2^(e[m] - 127) (pso_quant_rows_fp8; activations per token, weights per output channel)."""
     require_cuda(x)
-    assert x.dtype == BF16 and x.dim() == 2
+    assert x.dtype == ELEM and x.dim() == 2
     M, Kd = x.shape
     if q is None:
         q = torch.empty((M, Kd), device=x.device, dtype=torch.uint8)
@@ -259,7 +259,7 @@ def gemm_fp8(a, w, *, a2=None, w2=None, tail_rows=0, tail_group_n=0, alpha=1.0, 
         K2 = w2[0].shape[1]
         assert a2[0].shape[0] == tr and w2[0].shape[0] == N
     if out is None:
-        out = torch.empty((M, N // 2 if geglu else N), device=aq.device, dtype=BF16)
+        out = torch.empty((M, N // 2 if geglu else N), device=aq.device, dtype=ELEM)
     e0 = _prof_begin()
     check(lib().pso_gemm_fp8(1 if geglu else 0, M, N, Kd, ptr(aq), _row_stride(aq), ptr(ae), ptr(wq), _row_stride(wq),
                              ptr(we), ptr(a2[0]) if a2 is not None else None,
@@ -377,7 +377,7 @@ class TnRankQueue:
 
 
 def conv2d(x, weight, *, x2=None, mode=CONV_NORMAL, stride=1, pad=None, out_hw=None, bias=None, rowbias=None,
-           resid=None, a2=None, w2=None, alpha=1.0, out=None, out_dtype=BF16, accumulate=False):
+           resid=None, a2=None, w2=None, alpha=1.0, out=None, out_dtype=ELEM, accumulate=False):
     """NHWC implicit-GEMM conv.  x [B,H,W,C1] (+ x2 [B,H,W,C2] concatenated on channels); weight [Cout,ks,ks,C1+C2].
     Returns [B,Ho,Wo,Cout]."""
     require_cuda(x, weight)
@@ -485,7 +485,7 @@ def pair_loss_fwd(mode, x, x_prev, eps_pol, eps_ref, coef, pref, beta, clip_eps,
 
 
 def pair_loss_bwd(mode, x, x_prev, eps_pol, coef, pref, beta, clip_eps, ws, grad_out=None, grad_scale=1.0,
-                  out_dtype=BF16):
+                  out_dtype=ELEM):
     _check_pair_operands(x, x_prev, eps_pol, coef, pref)
     P = x.shape[0] // 2
     n = x[0].numel()
@@ -534,7 +534,7 @@ def db_loss_fwd(loss_type, eps, noisy, x0, sigma, beta, neg_defactor, prior_w, w
 
 
 def db_loss_bwd(loss_type, eps, noisy, x0, sigma, beta, neg_defactor, prior_w, ws, grad_out=None, grad_scale=1.0,
-                out_dtype=BF16):
+                out_dtype=ELEM):
     B = eps.shape[0] // 2
     n = eps[0].numel()
     deps = torch.empty(eps.shape, device=eps.device, dtype=out_dtype)
@@ -664,7 +664,7 @@ def silu(x):
 def timestep_embedding(t, dim, out=None, out_col=0):
     t = t.reshape(-1).float().contiguous()
     if out is None:
-        out = torch.empty((t.shape[0], dim), device=t.device, dtype=BF16)
+        out = torch.empty((t.shape[0], dim), device=t.device, dtype=ELEM)
     check(lib().pso_timestep_embedding(t.shape[0], dim, ptr(t), ptr(out), out.stride(0), out_col, stream_ptr()),
           "pso_timestep_embedding")
     return out
@@ -718,7 +718,7 @@ def transpose(x, out=None, pad_rows_to=1):
     Rp = -(-R // pad_rows_to) * pad_rows_to
     if out is None:
         out = torch.empty((C, Rp), device=x.device, dtype=x.dtype)
-    if _TRANSPOSE_BATCH is not None and Rp == R and x.dtype == torch.bfloat16 and R > 0 and C > 0:
+    if _TRANSPOSE_BATCH is not None and Rp == R and x.dtype == ELEM and R > 0 and C > 0:
         _row_stride(x)
         _row_stride(out)
         _TRANSPOSE_BATCH.append((x, out))
@@ -802,7 +802,7 @@ def im2col_conv(x, x2=None, mode=CONV_NORMAL, stride=1, pad=1, out_hw=None):
     if out_hw is None:
         out_hw = (2 * H, 2 * W) if mode == CONV_UP2 else ((H + 2 * pad - 3) // stride + 1, (W + 2 * pad - 3) // stride + 1)
     Ho, Wo = out_hw
-    out = torch.empty((B * Ho * Wo, 9 * (C1 + C2)), device=x.device, dtype=BF16)
+    out = torch.empty((B * Ho * Wo, 9 * (C1 + C2)), device=x.device, dtype=ELEM)
     check(lib().pso_im2col_conv(mode, B, ptr(x.contiguous()), C1, ptr(x2.contiguous()) if x2 is not None else None, C2,
                                 H, W, Ho, Wo, stride, pad, ptr(out), out.stride(0), stream_ptr()), "pso_im2col_conv")
     return out
@@ -813,7 +813,7 @@ def add(x, z):
 
 
 def cast_f32_bf16(x, scale=1.0, out=None):
-    out = torch.empty(x.shape, device=x.device, dtype=BF16) if out is None else out
+    out = torch.empty(x.shape, device=x.device, dtype=ELEM) if out is None else out
     check(lib().pso_cast_f32_bf16(x.numel(), ptr(x.contiguous()), float(scale), ptr(out), stream_ptr()),
           "pso_cast_f32_bf16")
     return out
@@ -861,7 +861,7 @@ def nchw_to_nhwc(x, pad_to=None, scale=1.0):
     """[B,C,H,W] fp32|bf16 -> [B,H,W,Cp] bf16 (channels zero-padded to Cp, values times scale)."""
     B, C, H, W = x.shape
     Cp = pad_to or C
-    out = torch.empty((B, H, W, Cp), device=x.device, dtype=BF16)
+    out = torch.empty((B, H, W, Cp), device=x.device, dtype=ELEM)
     check(lib().pso_nchw_to_nhwc(B, C, Cp, H * W, ptr(x.contiguous()), dtype_code(x), float(scale), ptr(out),
                                  stream_ptr()), "pso_nchw_to_nhwc")
     return out
@@ -1043,7 +1043,7 @@ def adamw8bit_step(param, grad, state, lr, betas, eps, weight_decay, step, grad_
     zeroes the gradient elements its blocks cover after reading them; returns whether it did."""
     require_cuda(param, grad)
     if out_bf16 is not None:
-        assert out_bf16.dtype == torch.bfloat16 and out_bf16.numel() == param.numel() and out_bf16.is_contiguous()
+        assert out_bf16.dtype == ELEM and out_bf16.numel() == param.numel() and out_bf16.is_contiguous()
     if state.desc is not None:
         fn = "pso_adamw8bit_step_blocks_zero_grad" if zero_grad else "pso_adamw8bit_step_blocks"
         check(getattr(lib(), fn)(param.numel(), state.nblk, ptr(state.desc), ptr(param), ptr(out_bf16),
@@ -1131,7 +1131,7 @@ def attention_small(q, k, v, B, S, H, causal, scale, out=None):
     HD = q.shape[1]
     D = HD // H
     if out is None:
-        out = torch.empty((B * S, HD), device=q.device, dtype=BF16)
+        out = torch.empty((B * S, HD), device=q.device, dtype=ELEM)
     sq, sk, sv, so = _row_stride(q), _row_stride(k), _row_stride(v), _row_stride(out)
     check(lib().pso_attention_small(B, H, S, D, ptr(q), sq, S * sq, ptr(k), sk, S * sk, ptr(v), sv, S * sv,
                                     int(bool(causal)), float(scale), ptr(out), so, S * so, stream_ptr()),
@@ -1140,7 +1140,7 @@ def attention_small(q, k, v, B, S, H, causal, scale, out=None):
 
 
 def activation_(x, mode):
-    assert x.is_contiguous() and x.dtype == BF16
+    assert x.is_contiguous() and x.dtype == ELEM
     check(lib().pso_activation(x.numel(), ptr(x), int(mode), stream_ptr()), "pso_activation")
     return x
 
@@ -1150,7 +1150,7 @@ def embed_tokens(ids, tok, pos):
     require_cuda(ids, tok, pos)
     B, S = ids.shape
     C = tok.shape[1]
-    out = torch.empty((B * S, C), device=tok.device, dtype=BF16)
+    out = torch.empty((B * S, C), device=tok.device, dtype=ELEM)
     check(lib().pso_embed_tokens(B, S, C, ptr(ids.contiguous()), ptr(tok), ptr(pos), ptr(out), stream_ptr()),
           "pso_embed_tokens")
     return out
@@ -1158,7 +1158,7 @@ def embed_tokens(ids, tok, pos):
 
 def embed_vision(patch, cls, pos, B, P):
     C = patch.shape[1]
-    out = torch.empty((B * (P + 1), C), device=patch.device, dtype=BF16)
+    out = torch.empty((B * (P + 1), C), device=patch.device, dtype=ELEM)
     check(lib().pso_embed_vision(B, P, C, ptr(patch), ptr(cls), ptr(pos), ptr(out), stream_ptr()), "pso_embed_vision")
     return out
 
@@ -1187,7 +1187,7 @@ def patchify(x, P, kpad):
     """processed pixel values NCHW [B, C, S, S] -> patch rows [B * (S/P)^2, kpad] bf16."""
     require_cuda(x)
     B, C, S, _ = x.shape
-    out = torch.empty((B * (S // P) ** 2, kpad), device=x.device, dtype=BF16)
+    out = torch.empty((B * (S // P) ** 2, kpad), device=x.device, dtype=ELEM)
     check(lib().pso_patchify(B, C, S, P, kpad, ptr(x.float().contiguous()), ptr(out), stream_ptr()), "pso_patchify")
     return out
 
@@ -1196,10 +1196,11 @@ def clip_preprocess(img, size, P, kpad, mean, std):
     """decoded images NHWC [B, H, W, 3] (bf16 / f32 in [-1, 1], or uint8) -> patch rows [B * (size/P)^2, kpad] bf16
     (uint8 quantisation, PIL bicubic resize, centre crop, rescale, normalise)."""
     require_cuda(img)
+    _lib.require_bf16("clip_preprocess (the reward models' image path; dtype code 2 means uint8 to this entry)")
     B, H, W, C = img.shape
-    assert C == 3 and img.dtype in (BF16, torch.float32, torch.uint8) and img.is_contiguous()
+    assert C == 3 and img.dtype in (ELEM, torch.float32, torch.uint8) and img.is_contiguous()
     ws = torch.empty(lib().pso_clip_preprocess_ws_bytes(B, H, W, size), device=img.device, dtype=torch.uint8)
-    out = torch.empty((B * (size // P) ** 2, kpad), device=img.device, dtype=BF16)
+    out = torch.empty((B * (size // P) ** 2, kpad), device=img.device, dtype=ELEM)
     m = (ctypes.c_float * 3)(*mean)
     sd = (ctypes.c_float * 3)(*std)
     code = 2 if img.dtype == torch.uint8 else dtype_code(img)  # PSO_U8

@@ -42,7 +42,7 @@ def distilled_step_with_logprob(
     mode = pso_core.dmd_mode(sample.dtype)
     coef = pso_core.dmd_coef(self.alphas_cumprod, timestep, prev_timestep, latent_dtype=sample.dtype)
     coef = coef.expand(sample.shape[0], -1).contiguous().to(model_output.device)
-    eps = model_output if model_output.dtype in (torch.float32, torch.bfloat16) else model_output.float()
+    eps = model_output if model_output.dtype in (torch.float32, K.ELEM) else model_output.float()
     x = sample.to(torch.float32)
     if prev_sample is None:
         # randn_tensor((1, C, H, W), dtype=sample.dtype) (:123-124): drawn in the latent dtype

@@ -25,7 +25,7 @@ def turbo_step_with_logprob(
 ):
     coef = pso_core.turbo_coef(self.sigmas, self.timesteps, timestep)
     coef = coef.expand(sample.shape[0], -1).contiguous().to(model_output.device)  # one timestep for the batch
-    eps = model_output if model_output.dtype in (torch.float32, torch.bfloat16) else model_output.float()
+    eps = model_output if model_output.dtype in (torch.float32, K.ELEM) else model_output.float()
     x = sample.to(torch.float32)
     if prev_sample is None:
         noise = torch.randn(model_output.shape, generator=generator, device=model_output.device,

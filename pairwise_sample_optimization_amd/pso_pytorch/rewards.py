@@ -10,7 +10,7 @@ from .. import kernels as K
 def light_reward():
     def _fn(images, prompts, metadata):
         if isinstance(images, torch.Tensor) and images.is_cuda:
-            x = images if images.dtype == torch.bfloat16 else images.to(torch.bfloat16)
+            x = images if images.dtype == K.ELEM else images.to(K.ELEM)
             r = K.row_mean(x.contiguous())
         else:
             r = torch.as_tensor(np.asarray(images)).reshape(len(images), -1).float().mean(1)

@@ -24,8 +24,10 @@ import torch.distributed as dist
 
 import os
 
+from . import _lib
 from . import kernels as K
 from . import pso_core
+from .amp import LossScaler, make_scaler
 from ._lib import MODE_TURBO, MODE_DMD
 from .schedulers import EulerAncestralDiscreteScheduler, LCMScheduler, dmd_distill_timesteps
 
@@ -44,7 +46,7 @@ def _ref_stream():
     return st
 
 
-BF16 = torch.bfloat16
+ELEM = _lib.ELEM_DTYPE  # the loaded library's 16-bit element type: bf16, or fp16 under PSO_LIB=f16
 
 
 def compute_time_ids(size, crop=0, device=None):
@@ -250,7 +252,7 @@ def _work_copy(unet, master):
     """The flat bf16 working copy that refresh() casts the master into (the optimizer can write it directly)."""
     st = unet.full if getattr(unet, "full", None) is not None else unet.lora
     w = getattr(st, "work", None)
-    ok = (w is not None and w.dtype == torch.bfloat16 and w.numel() == master.numel() and w.is_contiguous()
+    ok = (w is not None and w.dtype == ELEM and w.numel() == master.numel() and w.is_contiguous()
           and w.data_ptr() % 16 == 0)
     return w if ok else None
 
@@ -267,7 +269,20 @@ def lora_optimizer_step(tr):
         tr.sync_armed = False
     else:
         scale = allreduce_grads(grad, tr.pg, getattr(tr, "allreduce_dtype", None))
+    scaler = getattr(tr, "scaler", None)
+    if scaler is not None:
+        # fp16 loss scaling (amp.LossScaler): the backward ran on loss * S, so unscale in the gradient read.  The norm
+        # of the all-reduced gradient is read back -- the one sync per optimizer step, where GradScaler.step syncs --
+        # and every rank sees the same value.  Non-finite: skip the step whole (parameters, moments / 8-bit state and
+        # opt_step untouched), drop the gradient, back the scale off (accelerate's inf-skip, T:344-350).
+        scale = scale / scaler.scale
     K.grad_clip_coef(grad, tr.max_grad_norm, grad_scale=scale, out=tr.clip_buf)
+    if scaler is not None:
+        found_inf = not math.isfinite(float(tr.clip_buf[0]))
+        scaler.update(found_inf)
+        if found_inf:
+            K.zero_(grad)
+            return
     tr.opt_step += 1
     cast = True
     if getattr(tr, "adam8", None) is not None:  # train.use_8bit_adam: bitsandbytes AdamW8bit (T:427-435)
@@ -291,8 +306,14 @@ class PSOTrainer:
                  weight_decay=1e-6, adam_eps=1e-8, max_grad_norm=1.0, gradient_accumulation_steps=1,
                  train_batch_size=1, num_reward=1, process_group=None, max_pass_images=16, ref_unet=None,
                  latent_dtype=torch.float32, allreduce_dtype=None, use_8bit_adam=False, overlap_sync=None,
-                 bucket_mb=32.0):
+                 bucket_mb=32.0, loss_scale=None):
         self.unet = unet
+        # loss_scale: None (no scaling), a float (initial scale) or an amp.LossScaler: dynamic loss scaling with
+        # inf-skip for fp16 training.  Active under the f16 library only -- bf16 has fp32's exponent range.
+        self.scaler = make_scaler(loss_scale)
+        if self.scaler is not None and ELEM != torch.float16:
+            raise ValueError("loss_scale is for fp16 training (PSO_LIB=f16, libpso_amd_f16.so); the loaded library "
+                             f"computes in {ELEM}")
         if mode not in ("turbo", "dmd"):
             raise ValueError(f"mode must be 'turbo' or 'dmd', got {mode!r}")
         # DMD2 with fp16 / bf16 latents: the reference's latent-dtype step / log-prob arithmetic (replay modes,
@@ -387,12 +408,20 @@ class PSOTrainer:
             import warnings
             warnings.warn(f"PSOTrainer.from_config: latent_dtype {latent_dtype} differs from the config's "
                           f"mixed_precision={mp!r} (reference latents: {cfg_dtype})")
+        loss_scale = None
+        if ELEM == torch.float16:
+            # the f16 library runs the reference's own recipe: fp16 UNet arithmetic, fp32 LoRA parameters, dynamic
+            # loss scaling with inf-skip.  A config that asks for another precision belongs to the bf16 library.
+            if mp != "fp16":
+                raise ValueError(f"the f16 library (PSO_LIB=f16) trains mixed_precision='fp16' configs only, got "
+                                 f"{mp!r}: unset PSO_LIB for the bf16 library")
+            loss_scale = LossScaler()
         return cls(unet, mode=mode, num_steps=config.sample.num_steps, beta=float(tr.beta), clip_eps=float(tr.eps),
                    lr=tr.learning_rate, betas=(tr.adam_beta1, tr.adam_beta2), weight_decay=tr.adam_weight_decay,
                    adam_eps=tr.adam_epsilon, max_grad_norm=tr.max_grad_norm,
                    gradient_accumulation_steps=tr.gradient_accumulation_steps, train_batch_size=tr.batch_size,
                    num_reward=num_reward, process_group=process_group, ref_unet=ref_unet, latent_dtype=latent_dtype,
-                   use_8bit_adam=bool(getattr(tr, "use_8bit_adam", False)))
+                   use_8bit_adam=bool(getattr(tr, "use_8bit_adam", False)), loss_scale=loss_scale)
 
     # ------------------------------------------------------------------------------------------------------------
     # coefficients of transition j (host float32 scalars, the reference's operation order)
@@ -562,7 +591,7 @@ class PSOTrainer:
                                    self.clip_eps, ws)
         # accelerator.backward divides by gradient_accumulation_steps (accelerate accelerator.py:2840)
         deps = K.pair_loss_bwd(self.mode, mb.x, mb.x_next, eps_pol, mb.coef, pref, self.beta, self.clip_eps, ws,
-                               grad_scale=count / self.gas_total)
+                               grad_scale=count / self.gas_total * self.loss_scale)
         if self.overlap_sync and self.auto_step and (self.n_micro + count) % self.gas_total == 0:
             rt.unit_done = self.buckets.hook(rt)  # the window's last backward: overlap the gradient all-reduce
             self.sync_armed = True
@@ -578,6 +607,12 @@ class PSOTrainer:
     # ------------------------------------------------------------------------------------------------------------
     def optimizer_step(self):
         lora_optimizer_step(self)
+
+    @property
+    def loss_scale(self):
+        """The factor on the loss in backward: a power of two, constant within an accumulation window (it changes
+        only in optimizer_step); 1.0 without a scaler."""
+        return 1.0 if self.scaler is None else self.scaler.scale
 
     _SB_TENSORS = ("x", "x_next", "unet_in", "enc", "pooled", "tid", "t", "coef", "rewards")
 
@@ -596,7 +631,8 @@ class PSOTrainer:
             # full-UNet training: the optimizer step rebuilds the kernel-layout weight caches as new tensors
             # (refresh_full -> prepare), which a captured graph would keep reading at their old addresses
             return self.train_epoch(sb, generator)
-        key = tuple((k, tuple(getattr(sb, k).shape)) for k in self._SB_TENSORS)
+        # the loss scale is a host float baked into the captured loss backward: a change re-captures (rare)
+        key = tuple((k, tuple(getattr(sb, k).shape)) for k in self._SB_TENSORS) + (("loss_scale", self.loss_scale),)
         g = getattr(self, "_graph", None)
         if g is None or self._graph_key != key:
             self._graph = None

@@ -27,9 +27,10 @@ from types import SimpleNamespace
 import torch
 import torch.nn as nn
 
+from . import _lib
 from . import kernels as K
 
-BF16 = torch.bfloat16
+ELEM = _lib.ELEM_DTYPE  # the loaded library's 16-bit element type: bf16, or fp16 under PSO_LIB=f16
 # batched (per gradient unit) LoRA weight-gradient launches; PSO_TN_BATCH=0 issues every product at once (A/B knob)
 TN_BATCH = os.environ.get("PSO_TN_BATCH", "1") != "0"
 
@@ -78,7 +79,7 @@ class UNetConfig:
 # parameter holders (diffusers names / layouts) + kernel-layout caches
 # ======================================================================================================================
 def _param(*shape):
-    return nn.Parameter(torch.empty(*shape, dtype=BF16), requires_grad=False)
+    return nn.Parameter(torch.empty(*shape, dtype=ELEM), requires_grad=False)
 
 
 def _uniform_(p, bound, g):
@@ -126,7 +127,7 @@ class Conv2d(nn.Module):
         elif self.cin % 64 != 0:  # conv_in: im2col GEMM, K = 9*Ci padded to 64
             kp = 64 * ((9 * self.cin + 63) // 64)
             self.kp = kp
-            self.w_col = torch.zeros(self.cout, kp, device=w.device, dtype=BF16)
+            self.w_col = torch.zeros(self.cout, kp, device=w.device, dtype=ELEM)
             self.w_col[:, :9 * self.cin] = self.w_nhwc.reshape(self.cout, -1)
         else:
             # input-gradient weights: stride 1 -> rotated taps; stride 2 -> unrotated taps (T2 gather)
@@ -134,7 +135,7 @@ class Conv2d(nn.Module):
             if self.cout % 64 != 0:  # conv_out (Co=4): the input-gradient conv has C=4 -> im2col GEMM
                 kp = 64 * ((9 * self.cout + 63) // 64)
                 self.kp_dx = kp
-                self.w_dx_col = torch.zeros(self.cin, kp, device=w.device, dtype=BF16)
+                self.w_dx_col = torch.zeros(self.cin, kp, device=w.device, dtype=ELEM)
                 self.w_dx_col[:, :9 * self.cout] = self.w_dx.reshape(self.cin, -1)
 
 
@@ -277,9 +278,9 @@ def _gemm_fwd(a, w, *, a2=None, w2=None, tail_group_n=0, tail_rows=0, bias=None,
                         for j in range(N // tail_group_n)], 1)
     else:
         lo = K.gemm(a2, w2)
-    base[:rows] = (base[:rows].float() + lo.float()).to(BF16)
+    base[:rows] = (base[:rows].float() + lo.float()).to(ELEM)
     if resid is not None:
-        base = (base.float() + resid.float()).to(BF16)
+        base = (base.float() + resid.float()).to(ELEM)
     return base  # ff.proj dW straight into the natural rows (pso_gemm_tn_geglu)
 
 
@@ -410,7 +411,7 @@ class LoraState:
         self.numel = off
         self.master = torch.zeros(off, device=device, dtype=torch.float32)
         self.grad = torch.zeros(off, device=device, dtype=torch.float32)
-        self.work = torch.zeros(off, device=device, dtype=BF16)
+        self.work = torch.zeros(off, device=device, dtype=ELEM)
         self.param = nn.Parameter(self.master, requires_grad=True)  # autograd trigger for the UNet node
         self.blk = {}
         pairs = []
@@ -420,15 +421,15 @@ class LoraState:
             ns.A_qkv, ns.sB_qkv, ns.A_o1, ns.sB_o1 = w("attn1.A_qkv"), w("attn1.B_qkv"), w("attn1.A_o"), w("attn1.B_o")
             ns.A_q2, ns.sB_q2, ns.A_kv2, ns.sB_kv2 = w("attn2.A_q"), w("attn2.B_q"), w("attn2.A_kv"), w("attn2.B_kv")
             ns.A_o2, ns.sB_o2 = w("attn2.A_o"), w("attn2.B_o")
-            ns.At_qkv = torch.empty(C, 3 * r, device=device, dtype=BF16)
-            ns.sBt_qkv = torch.empty(r, 3 * C, device=device, dtype=BF16)
-            ns.At_o1 = torch.empty(C, r, device=device, dtype=BF16)
-            ns.sBt_o1 = torch.empty(r, C, device=device, dtype=BF16)
-            ns.At_q2 = torch.empty(C, r, device=device, dtype=BF16)
-            ns.sBt_q2 = torch.empty(r, C, device=device, dtype=BF16)
-            ns.sBt_kv2 = torch.empty(r, 2 * C, device=device, dtype=BF16)
-            ns.At_o2 = torch.empty(C, r, device=device, dtype=BF16)
-            ns.sBt_o2 = torch.empty(r, C, device=device, dtype=BF16)
+            ns.At_qkv = torch.empty(C, 3 * r, device=device, dtype=ELEM)
+            ns.sBt_qkv = torch.empty(r, 3 * C, device=device, dtype=ELEM)
+            ns.At_o1 = torch.empty(C, r, device=device, dtype=ELEM)
+            ns.sBt_o1 = torch.empty(r, C, device=device, dtype=ELEM)
+            ns.At_q2 = torch.empty(C, r, device=device, dtype=ELEM)
+            ns.sBt_q2 = torch.empty(r, C, device=device, dtype=ELEM)
+            ns.sBt_kv2 = torch.empty(r, 2 * C, device=device, dtype=ELEM)
+            ns.At_o2 = torch.empty(C, r, device=device, dtype=ELEM)
+            ns.sBt_o2 = torch.empty(r, C, device=device, dtype=ELEM)
             pairs += [(ns.A_qkv, ns.At_qkv), (ns.sB_qkv, ns.sBt_qkv), (ns.A_o1, ns.At_o1), (ns.sB_o1, ns.sBt_o1),
                       (ns.A_q2, ns.At_q2), (ns.sB_q2, ns.sBt_q2), (ns.sB_kv2, ns.sBt_kv2), (ns.A_o2, ns.At_o2),
                       (ns.sB_o2, ns.sBt_o2)]
@@ -439,8 +440,8 @@ class LoraState:
         by_c = {}
         for path, C, Dc in blocks:
             by_c.setdefault(C, []).append(self.blk[path])
-        self.kv_stacks = {C: (torch.empty(len(bl) * 2 * r, bl[0].A_kv2.shape[1], device=device, dtype=BF16),
-                              torch.empty(len(bl) * 2 * C, r, device=device, dtype=BF16), bl)
+        self.kv_stacks = {C: (torch.empty(len(bl) * 2 * r, bl[0].A_kv2.shape[1], device=device, dtype=ELEM),
+                              torch.empty(len(bl) * 2 * C, r, device=device, dtype=ELEM), bl)
                           for C, bl in by_c.items()}
         self._b_views = [self.seg(self.work, p, k) for p, _, _ in blocks for k in self.layout[p] if ".B_" in k]
 
@@ -665,7 +666,7 @@ class BasicTransformerBlock(nn.Module):
         # --- GEGLU feed-forward ---
         n3, st3 = K.layer_norm_fwd(h2, self.norm3.weight, self.norm3.bias, 1e-5)
         ff = self.ff
-        f = torch.empty((Mp, ff.w_int.shape[0]), device=x.device, dtype=BF16) if rt.save else None
+        f = torch.empty((Mp, ff.w_int.shape[0]), device=x.device, dtype=ELEM) if rt.save else None
         if ok8(ff.w_int.shape[0], C, "ff") and fp8_geglu_pays(M, ff.w_int.shape[0]):
             gg = K.gemm_fp8(K.quant_rows_fp8(n3), f8((id(self), "ff"), ff.w_int), bias=ff.b_int, geglu=True, out_pre=f,
                             pre_rows=Mp)
@@ -739,7 +740,7 @@ class BasicTransformerBlock(nn.Module):
         enc = rt.enc
         Se = enc.shape[0] // B
         kv3 = sv["kv3"]
-        dkv2 = torch.empty((B * Se, 2 * C), device=dh3.device, dtype=BF16)
+        dkv2 = torch.empty((B * Se, 2 * C), device=dh3.device, dtype=ELEM)
         dk3 = dkv2.view(B, Se, 2 * C)
         dq2, _, _ = K.attention_bwd(sv["q2"].view(B, S, C), kv3[..., :C], kv3[..., C:], sv["a2"].view(B, S, C),
                                     sv["lse2"], da2.view(B, S, C), a2m.heads, dk=dk3[..., :C], dv=dk3[..., C:])
@@ -788,7 +789,7 @@ class BasicTransformerBlock(nn.Module):
         if fg is not None:
             _lin_dw(fg, o1, dh1, sv["a1"], rt)
         q3 = sv["qkv"].view(B, S, 3 * C)
-        dqkv = torch.empty((M, 3 * C), device=dh3.device, dtype=BF16)
+        dqkv = torch.empty((M, 3 * C), device=dh3.device, dtype=ELEM)
         d3 = dqkv.view(B, S, 3 * C)
         K.attention_bwd(q3[..., :C], q3[..., C:2 * C], q3[..., 2 * C:], sv["a1"].view(B, S, C), sv["lse1"],
                         da1.view(B, S, C), a1m.heads, dq=d3[..., :C], dk=d3[..., C:2 * C], dv=d3[..., 2 * C:])
@@ -1112,7 +1113,7 @@ class UNet2DConditionModel(nn.Module):
 
     def load_state_dict(self, sd, strict=True):
         sd = {self._remap_key(k): v for k, v in sd.items()}
-        res = super().load_state_dict({k: v.to(BF16) for k, v in sd.items()}, strict=strict)
+        res = super().load_state_dict({k: v.to(ELEM) for k, v in sd.items()}, strict=strict)
         self._prepared = False
         return res
 
@@ -1239,6 +1240,7 @@ class UNet2DConditionModel(nn.Module):
         """Train every UNet parameter (BASELINE C3 / C4; the reference has no such path, App. A #4): flat fp32
         master + grad over named_parameters; backward_nhwc then accumulates every weight gradient into self.full.grad
         and runs down to conv_in.  Adapters, if any, must be absent."""
+        _lib.require_bf16("full-UNet training (enable_full_grads)")
         if self.lora is not None:
             raise ValueError("full-UNet training and LoRA adapters are exclusive")
         self.full = FullGradState(self)
@@ -1315,6 +1317,8 @@ class UNet2DConditionModel(nn.Module):
         carries a 7.5e-2 LoRA-gradient error (cross q 5.6e-3, GEGLU proj 3.5e-2; tools/diag_fp8_grads.py) while running
         slower than bf16.  Shapes the fp8 kernel does not take (N % 256 or K % 128 != 0) stay bf16.  LoRA training
         only (the base weights are quantised once and cached)."""
+        if on:
+            _lib.require_bf16("the fp8 forward (enable_fp8_forward / DreamBooth fp8=)")
         if on and self.full is not None:
             raise ValueError("fp8 forward: LoRA training only (the full-UNet mode updates the base weights)")
         self.fp8 = bool(on)
@@ -1387,7 +1391,7 @@ class UNet2DConditionModel(nn.Module):
         s1 = K.silu(t1)
         emb = K.gemm(s1, l2.weight, bias=l2.bias)
         tid = K.timestep_embedding(time_ids.reshape(-1), cfg.addition_time_embed_dim).view(B, -1)
-        add_in = K.concat_channels(text_embeds.to(BF16).contiguous(), tid)
+        add_in = K.concat_channels(text_embeds.to(ELEM).contiguous(), tid)
         a1, a2 = self.add_embedding.linear_1, self.add_embedding.linear_2
         u1 = K.gemm(add_in, a1.weight, bias=a1.bias)
         s2 = K.silu(u1)
@@ -1408,7 +1412,7 @@ class UNet2DConditionModel(nn.Module):
             self.prepare()
         B = x.shape[0]
         lora_on = self.lora is not None and self._adapters_enabled
-        encf = enc.to(BF16).reshape(B * enc.shape[1], enc.shape[2]).contiguous()
+        encf = enc.to(ELEM).reshape(B * enc.shape[1], enc.shape[2]).contiguous()
         rt = self._runtime(B, encf, save, lora_on)
         temb_all = self._embed(timestep, time_ids, text_embeds, B, x.device)
         tb = lambda m: temb_all[:, m._temb_off:m._temb_off + m.cout]
@@ -1485,7 +1489,7 @@ class UNet2DConditionModel(nn.Module):
         if fg is not None:
             rt.dtemb = torch.zeros((B, self._temb_n), device=dout.device, dtype=torch.float32)
             co = self.conv_out.cout
-            dy8 = torch.zeros((B * H * W, 8), device=dout.device, dtype=BF16)  # TN operands need 8 | width
+            dy8 = torch.zeros((B * H * W, 8), device=dout.device, dtype=ELEM)  # TN operands need 8 | width
             dy8[:, :co] = dout.reshape(-1, co)
             _conv_dw(fg, self.conv_out, dy8, sv["hn"], rt, K.im2col_conv)
             dh = K.group_norm_bwd(sv["h"], dhn, sv["st"], self.conv_norm_out.weight, self.conv_norm_out.bias, True,
@@ -1593,7 +1597,7 @@ class UNet2DConditionModel(nn.Module):
         def silu_bwd(dy, x):
             xf = x.float()
             sg = torch.sigmoid(xf)
-            return (dy.float() * sg * (1 + xf * (1 - sg))).to(BF16)
+            return (dy.float() * sg * (1 + xf * (1 - sg))).to(ELEM)
 
         demb = silu_bwd(K.gemm(dt, self._temb_wt), e["emb"])  # d emb (pre-silu), [B, tdim]
         a1, a2 = self.add_embedding.linear_1, self.add_embedding.linear_2

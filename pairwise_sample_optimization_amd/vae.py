@@ -25,10 +25,11 @@ from types import SimpleNamespace
 import torch
 import torch.nn as nn
 
+from . import _lib
 from . import kernels as K
 from .unet import Conv2d, Linear, Norm, ResnetBlock2D, Upsample2D
 
-BF16 = torch.bfloat16
+ELEM = _lib.ELEM_DTYPE  # the loaded library's 16-bit element type: bf16, or fp16 under PSO_LIB=f16
 
 
 @dataclass
@@ -202,7 +203,7 @@ class AutoencoderKL(nn.Module):
     def load_state_dict(self, sd, strict=True):
         """diffusers AutoencoderKL keys (encoder.*, quant_conv.*, post_quant_conv.*, decoder.*).  A decoder-only
         state dict loads with strict=False (the encoder keeps its init)."""
-        sd = {k: v.to(BF16) for k, v in sd.items()}
+        sd = {k: v.to(ELEM) for k, v in sd.items()}
         res = super().load_state_dict(sd, strict=strict)
         self._prepared = False
         return res
@@ -220,7 +221,7 @@ class AutoencoderKL(nn.Module):
         lc = self.cfg.latent_channels
         self._lc_pad = 8 * ((lc + 7) // 8)
         w = self.post_quant_conv.weight.data.reshape(lc, lc)
-        self._pq_w = torch.zeros(lc, self._lc_pad, device=w.device, dtype=BF16)
+        self._pq_w = torch.zeros(lc, self._lc_pad, device=w.device, dtype=ELEM)
         self._pq_w[:, :lc] = w
         d.conv_out.prepare()
         self._prepared = True
@@ -245,7 +246,7 @@ class AutoencoderKL(nn.Module):
         per = max(1, (1 << 30) // per_img)
         if B <= per:
             return self._decode_chunk(zp)
-        out = torch.empty((B, 8 * h, 8 * w, self.cfg.out_channels), device=zp.device, dtype=BF16)
+        out = torch.empty((B, 8 * h, 8 * w, self.cfg.out_channels), device=zp.device, dtype=ELEM)
         for i in range(0, B, per):  # conv_out writes each chunk's rows of the batch output in place
             self._decode_chunk(zp[i:i + per], out=out[i:i + per])
         return out

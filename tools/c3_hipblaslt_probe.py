@@ -14,9 +14,9 @@ N_LIB = [0]
 
 
 def gemm(a, w, *, bias=None, resid=None, a2=None, w2=None, alpha=1.0, rowbias=None, rows_per_group=1, out=None,
-         out_dtype=K.BF16, accumulate=False, tail_group_n=0, tail_rows=0):
+         out_dtype=K.ELEM, accumulate=False, tail_group_n=0, tail_rows=0):
     plain = (bias is None and resid is None and a2 is None and rowbias is None and alpha == 1.0 and out is None and
-             out_dtype == K.BF16 and not accumulate and a.shape[0] >= 2048)
+             out_dtype == K.ELEM and not accumulate and a.shape[0] >= 2048)
     if plain and os.environ.get("PROBE_LIB") == "1":
         N_LIB[0] += 1
         return torch.mm(a, w.t())
