@@ -19,6 +19,11 @@
 // (x0_pred - x0).
 #include "common.h"
 
+// Element-wise op order mirrors the reference's separate torch ops (no FMA contraction), as in pso_loss.hip: a fused
+// eps * (-sigma) + noisy differs from the two-rounding form by an ulp of |sigma eps|, which the cancellation against
+// x0 turns into up to 1e-5 of a per-image loss when an image has few elements (nothing averages it out).
+#pragma clang fp contract(off)
+
 #define DB_CHUNK 8192
 #define DB_THREADS 256
 

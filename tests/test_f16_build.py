@@ -150,14 +150,16 @@ def test_loss_scale_needs_the_f16_library(cuda):
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_f16_library_on_gpu(cuda, capsys):
-    """tests/test_gpu_f16.py in one fresh child process on libpso_amd_f16.so (PSO_LIB=f16): -x, so a fault ends the
-    child at once; the child's whole log is written to $PSO_TEST_LOG_DIR/f16_child.log when that variable names a
-    directory (the failure message carries its tail either way)."""
+    """tests/test_gpu_f16.py and tests/test_gpu_loss_kernels.py in one fresh child process on libpso_amd_f16.so
+    (PSO_LIB=f16): -x, so a fault ends the child at once; the child's whole log is written to
+    $PSO_TEST_LOG_DIR/f16_child.log when that variable names a directory (the failure message carries its tail
+    either way)."""
     assert os.path.exists(F16_LIB), "libpso_amd_f16.so not built (make -C pairwise_sample_optimization_amd/csrc)"
     env = dict(os.environ, PSO_LIB="f16")
     env.pop("PSO_LIB_PATH", None)
     cmd = [sys.executable, "-u", "-m", "pytest", "-x", "-q", "-s", "-p", "no:cacheprovider", "--timeout", "300",
-           "--timeout-method", "thread", "-m", "gpu", os.path.join(ROOT, "tests", "test_gpu_f16.py")]
+           "--timeout-method", "thread", "-m", "gpu", os.path.join(ROOT, "tests", "test_gpu_f16.py"),
+           os.path.join(ROOT, "tests", "test_gpu_loss_kernels.py")]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=840)
     tail = r.stdout[-6000:] + r.stderr[-2000:]
     with capsys.disabled():  # the child's summary line belongs in the suite log

@@ -11,16 +11,23 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("loss_type", ["pso", "pso_db"])
-@pytest.mark.parametrize("B,h,eps_bf16", [(1, 64, True), (2, 32, False), (3, 16, True)])
-def test_db_loss_fwd_bwd_vs_oracle(cuda, loss_type, B, h, eps_bf16):
+# the first three keep their ids from when the shape was (2B, 4, h, h): B-h-eps_bf16, seed 100 B + h
+@pytest.mark.parametrize("B,n,seed,eps_bf16", [
+    pytest.param(1, 4 * 64 * 64, 164, True, id="1-64-True"), pytest.param(2, 4 * 32 * 32, 232, False, id="2-32-False"),
+    pytest.param(3, 4 * 16 * 16, 316, True, id="3-16-True"),
+    (1, 8196, 1, True), (1, 8196, 1, False),        # second chunk of 4 elements (DB_CHUNK = 8192)
+    (2, 17412, 2, True), (2, 17412, 2, False),      # three chunks, the last ragged against the thread stride
+    (300, 4, 3, True), (300, 4, 3, False),          # the finalize loops over pairs take a second trip
+    (1024, 4, 4, True), (1024, 4, 4, False)])       # ... and fill the 1024-entry LDS tables
+def test_db_loss_fwd_bwd_vs_oracle(cuda, loss_type, B, n, seed, eps_bf16):
     from pairwise_sample_optimization_amd import kernels as K
-    rng = np.random.default_rng(B * 100 + h)
-    shape = (2 * B, 4, h, h)
+    rng = np.random.default_rng(seed)
+    shape = (2 * B, n)
     sig = rng.choice([14.614647, 4.081731, 1.612887, 0.693205], size=B).astype(np.float32)
     sigma = np.concatenate([sig, sig])
     x0 = rng.standard_normal(shape).astype(np.float32)
     noise = rng.standard_normal(shape).astype(np.float32)
-    noisy = (x0 + noise * sigma[:, None, None, None]).astype(np.float32)
+    noisy = (x0 + noise * sigma[:, None]).astype(np.float32)
     eps = (noise + 0.05 * rng.standard_normal(shape)).astype(np.float32)
     eps_ref = (noise + 0.05 * rng.standard_normal(shape)).astype(np.float32)
     if eps_bf16:  # the kernel reads the UNet's bf16 output; give the oracle the same rounded values
@@ -42,3 +49,15 @@ def test_db_loss_fwd_bwd_vs_oracle(cuda, loss_type, B, h, eps_bf16):
     assert abs(loss.item() - rloss) <= 2e-5 * abs(rloss) + 1e-7
     g = deps.cpu().numpy()
     assert np.abs(g - rg).max() <= 1e-4 * np.abs(rg).max() + 1e-12
+
+
+def test_db_loss_rejects_more_than_1024_pairs(cuda):
+    from pairwise_sample_optimization_amd import kernels as K, _lib
+    B = 1025
+    e = torch.zeros((2 * B, 4), device=cuda)
+    s = torch.ones(2 * B, device=cuda)
+    ws = K.db_loss_ws(B, 4, cuda)
+    with pytest.raises(_lib.PsoLibError):
+        K.db_loss_fwd(K.DB_HINGE, e, e, e, s, 5.0, 0.1, 0.5, ws)
+    with pytest.raises(_lib.PsoLibError):
+        K.db_loss_bwd(K.DB_HINGE, e, e, e, s, 5.0, 0.1, 0.5, ws)
