@@ -384,6 +384,17 @@ int pso_conv_weight_t(int Co, int ks, int Ci, int flip, const void* w, void* wt,
 /* batched transpose: descs = device array of n {const bf16* src; bf16* dst; int R, C; long ldi, ldo;} (src [R][C]
  * -> dst [C][R]); one launch for all LoRA working-copy transposes after an optimizer step. */
 int pso_transpose_batched(int n, const void* descs, int max_r, int max_c, void* stream);
+/* LoRA ranks below 8 (csrc/lora_pad.hip): the optimizer's flat fp32 tensors keep peft's shapes, the kernels read
+ * working copies zero-padded to rank 8.  descs = device array of n 48-B records {float* logical; void* padded;
+ * int R, C, Rp, Cp; long ld; int scaled, reserved;}: logical [R][C] fp32 with contiguous rows at any 4-B boundary,
+ * padded [Rp][Cp] with row stride ld, 16-B aligned, Cp % 8 == 0, ld % 8 == 0.  One launch for all matrices, no host
+ * synchronisation, no allocation (hipGraph-capturable).
+ * pso_lora_pack: padded (16-bit elements) = ELEM(logical), and for records with scaled != 0 and scale != 1
+ *   ELEM(scale * ELEM(logical)) (the cast followed by pso_axpby); pad rows / columns = 0.  max_items >= max Rp*Cp/8.
+ * pso_lora_grad_fold: logical += padded[:R, :C] (fp32, one add per element), then padded[Rp][Cp] = 0.
+ *   max_items >= max Rp*Cp/4. */
+int pso_lora_pack(int n, const void* descs, long max_items, float scale, void* stream);
+int pso_lora_grad_fold(int n, const void* descs, long max_items, void* stream);
 /* many transposes in one launch over a flat grid of 64 x 64 tiles: descs = device array of n 48-B records
  * {const bf16* src; bf16* dst; long ldi, ldo; int R, C, tiles_c, tile0;} (src [R][C] -> dst [C][R], tiles_c =
  * ceil(C / 64), tile0 = the record's first tile, ascending from 0), total_tiles = sum of ceil(R/64) * tiles_c. */

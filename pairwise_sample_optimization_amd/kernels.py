@@ -1100,6 +1100,57 @@ class BatchedTranspose:
                   "pso_transpose_batched")
 
 
+class LoraPadTable:
+    """A fixed list of (logical [R,C] fp32, padded [Rp,Cp], scaled) matrix pairs of a LoRA state whose rank is below
+    the kernels' 8-wide granule (descriptor table on device, built once: the buffers are persistent).  `pack` fills
+    16-bit padded working copies from the logical fp32 tensors (pso_lora_pack), `fold` adds fp32 padded gradient
+    scratch into the logical gradients and clears it (pso_lora_grad_fold); each is ONE launch over all matrices, or
+    over the records [first, first + count)."""
+
+    RECORD = 48
+
+    def __init__(self, entries, device, padded_dtype):
+        import numpy as np
+        dt = np.dtype([("logical", "<u8"), ("padded", "<u8"), ("R", "<i4"), ("C", "<i4"), ("Rp", "<i4"), ("Cp", "<i4"),
+                       ("ld", "<i8"), ("scaled", "<i4"), ("reserved", "<i4")])
+        assert dt.itemsize == self.RECORD
+        arr = np.zeros(len(entries), dtype=dt)
+        self.sizes = []
+        for i, (lo, pd, scaled) in enumerate(entries):
+            require_cuda(lo, pd)
+            R, C = lo.shape
+            Rp, Cp = pd.shape
+            assert lo.dtype == torch.float32 and lo.is_contiguous() and pd.dtype == padded_dtype
+            assert Rp >= R and Cp >= C and Cp % 8 == 0 and pd.stride(1) == 1 and pd.stride(0) % 8 == 0 \
+                and pd.stride(0) >= Cp and pd.data_ptr() % 16 == 0, "padded LoRA matrices need 16-byte rows"
+            arr[i] = (lo.data_ptr(), pd.data_ptr(), R, C, Rp, Cp, pd.stride(0), int(bool(scaled)), 0)
+            self.sizes.append(Rp * Cp)
+        self.n = len(entries)
+        self.keep = entries
+        self.padded_dtype = padded_dtype
+        self._ranges = {}
+        self.desc = torch.from_numpy(arr.view(np.uint8)).to(device)
+
+    def _range(self, first, count):
+        count = self.n - first if count is None else count
+        hit = self._ranges.get((first, count))
+        if hit is None:
+            assert 0 <= first and count > 0 and first + count <= self.n
+            hit = self._ranges[(first, count)] = (count, self.desc.data_ptr() + first * self.RECORD,
+                                                  max(self.sizes[first:first + count]))
+        return hit
+
+    def pack(self, scale=1.0, first=0, count=None):
+        assert self.padded_dtype == ELEM
+        count, descs, size = self._range(first, count)
+        check(lib().pso_lora_pack(count, descs, size // 8, float(scale), stream_ptr()), "pso_lora_pack")
+
+    def fold(self, first=0, count=None):
+        assert self.padded_dtype == torch.float32
+        count, descs, size = self._range(first, count)
+        check(lib().pso_lora_grad_fold(count, descs, size // 4, stream_ptr()), "pso_lora_grad_fold")
+
+
 def transpose_batched(x, out=None):
     """[Z, R, C] (rows contiguous) -> [Z, C, R] bf16 in one launch (a descriptor per matrix)."""
     Z, R, C = x.shape

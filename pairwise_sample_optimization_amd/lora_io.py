@@ -62,6 +62,12 @@ def load_lora_into_unet(state_dict, network_alphas, unet):
     missing = [n for n in st.adapter_names() if f"{n}.lora_A.weight" not in sd or f"{n}.lora_B.weight" not in sd]
     if missing:
         raise KeyError(f"LoRA state dict lacks {len(missing)} adapters, e.g. {missing[0]}")
+    for n in st.adapter_names():
+        A, B = sd[f"{n}.lora_A.weight"], sd[f"{n}.lora_B.weight"]
+        if A.dim() != 2 or B.dim() != 2 or A.shape[0] != st.r or B.shape[1] != st.r:
+            raise ValueError(f"LoRA state dict has rank {A.shape[0] if A.dim() == 2 else tuple(A.shape)} adapters "
+                             f"({n}: lora_A {tuple(A.shape)}, lora_B {tuple(B.shape)}), the unet's adapter has rank "
+                             f"{st.r}: add the adapter with LoraConfig(r=<the file's rank>)")
     dev = st.master.device
     st.load_peft({k: v.to(dev, torch.float32) for k, v in sd.items()})
 

@@ -240,11 +240,11 @@ def trainable_segments(unet):
         fg = unet.full
         return [(fg.offsets[nm][0], p.numel()) for nm, p in zip(fg.names, fg.params)]
     st = unet.lora
-    base = st.master.data_ptr()
+    base = st.master.storage_offset()  # (element offsets: also defined for a meta-device state)
     segs = []
     for name in st.adapter_names():
         for t in st.adapter_views(st.master, name):
-            segs.append(((t.data_ptr() - base) // st.master.element_size(), t.numel()))
+            segs.append((t.storage_offset() - base, t.numel()))
     return segs
 
 

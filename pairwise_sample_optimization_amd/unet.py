@@ -360,8 +360,9 @@ def check_lora_config(cfg):
         return getattr(cfg, name, ref)
 
     r = get("r", 32)
-    if isinstance(r, bool) or not isinstance(r, int) or r <= 0 or r % 8:
-        raise ValueError(f"LoraConfig.r must be a positive multiple of 8 (the rank kernels' granule), got {r!r}")
+    if isinstance(r, bool) or not isinstance(r, int) or r <= 0 or (r % 8 and r > 7):
+        raise ValueError("LoraConfig.r must be 1..7 or a positive multiple of 8 (the rank kernels' granule; the "
+                         f"narrow ranks run zero-padded to it), got {r!r}")
     alpha = get("lora_alpha", r)
     if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not alpha > 0:
         raise ValueError(f"LoraConfig.lora_alpha must be a positive number, got {alpha!r}")
@@ -392,31 +393,56 @@ class LoraState:
     gradients); inside a block the adapters that are used together are adjacent so their stacks are plain views:
       attn1: [A_q A_k A_v] (3r x C) [B_q B_k B_v] (3C x r) A_o B_o | attn2: A_q B_q [A_k A_v] [B_k B_v] A_o B_o
     After each optimizer step `refresh()` = one cast kernel + one batched-transpose kernel for the transposed forms the
-    backward GEMMs need (A^T, (sB)^T)."""
+    backward GEMMs need (A^T, (sB)^T).
+
+    Ranks 1..7 (diffusers' default 4): master and grad stay LOGICAL -- peft's tensors exactly, no pads -- so the
+    optimizer (per-tensor 8-bit blocks, the 4096-element 32-bit threshold), the clip norm, the all-reduce and the
+    checkpoints are peft's.  The working copy, its transposes, the k/v stacks and an fp32 gradient scratch `grad_pad`
+    are PADDED to r_pad = 8 with zero rows of A / zero columns of B: numerically the same adapter, on the rank-8
+    kernels.  refresh() packs master -> work (pso_lora_pack); the backward's products land in grad_pad and are folded
+    into grad per gradient unit (fold_grads, pso_lora_grad_fold).  r, scale = alpha / r and the init std 1 / r are the
+    logical rank's; for multiples of 8 r_pad == r, the layouts coincide and nothing of this runs."""
 
     def __init__(self, blocks, r, alpha, device):
         self.r, self.alpha, self.scale = r, alpha, alpha / r
+        # the rank the kernels see: 8 (16-byte rows of the 16-bit operands, the 8-wide K granule of the K-tail / skinny
+        # / TN kernels) for r < 8, with zero rows of A and zero columns of B beyond r; r itself otherwise.  8 and not
+        # 16: rank 8 already runs everywhere (plain TN launches instead of the rank-16 streaming kernel), and 16 would
+        # double every rank-side byte for no kernel that needs it
+        self.r_pad = rp = r if r % 8 == 0 else 8
         self.blocks = blocks  # [(path, C, Dc)] forward order
-        self.layout = {}
-        off = 0
-        for path, C, Dc in reversed(blocks):
-            segs = {}
-            for key, rows, cols in (("attn1.A_qkv", 3 * r, C), ("attn1.B_qkv", 3 * C, r), ("attn1.A_o", r, C),
-                                    ("attn1.B_o", C, r), ("attn2.A_q", r, C), ("attn2.B_q", C, r),
-                                    ("attn2.A_kv", 2 * r, Dc), ("attn2.B_kv", 2 * C, r), ("attn2.A_o", r, C),
-                                    ("attn2.B_o", C, r)):
-                segs[key] = (off, rows, cols)
-                off += rows * cols
-            self.layout[path] = segs
+
+        def lay(k):
+            out, off = {}, 0
+            for path, C, Dc in reversed(blocks):
+                segs = {}
+                for key, rows, cols in (("attn1.A_qkv", 3 * k, C), ("attn1.B_qkv", 3 * C, k), ("attn1.A_o", k, C),
+                                        ("attn1.B_o", C, k), ("attn2.A_q", k, C), ("attn2.B_q", C, k),
+                                        ("attn2.A_kv", 2 * k, Dc), ("attn2.B_kv", 2 * C, k), ("attn2.A_o", k, C),
+                                        ("attn2.B_o", C, k)):
+                    segs[key] = (off, rows, cols)
+                    off += rows * cols
+                out[path] = segs
+            return out, off
+
+        # logical layout: peft's tensors back to back (what the optimizer, the all-reduce, the clip and the checkpoints
+        # see); padded layout: the same segments at rank r_pad (what the kernels read and write).  One and the same
+        # for the multiples of 8.
+        self.layout, off = lay(r)
+        self.pad_layout, poff = (self.layout, off) if rp == r else lay(rp)
         self.numel = off
         self.master = torch.zeros(off, device=device, dtype=torch.float32)
         self.grad = torch.zeros(off, device=device, dtype=torch.float32)
-        self.work = torch.zeros(off, device=device, dtype=ELEM)
+        self.work = torch.zeros(poff, device=device, dtype=ELEM)
+        # r < 8: the weight-gradient products accumulate into this fp32 scratch in the padded layout; fold_grads adds
+        # each gradient unit's part into `grad` and clears it.  All zero outside a backward.
+        self.grad_pad = torch.zeros(poff, device=device, dtype=torch.float32) if rp != r else None
         self.param = nn.Parameter(self.master, requires_grad=True)  # autograd trigger for the UNet node
         self.blk = {}
         pairs = []
+        r = rp  # from here on: the kernels' view
         for path, C, Dc in blocks:
-            w = lambda k: self.seg(self.work, path, k)
+            w = lambda k: self.seg(self.work, path, k, padded=True)
             ns = SimpleNamespace()
             ns.A_qkv, ns.sB_qkv, ns.A_o1, ns.sB_o1 = w("attn1.A_qkv"), w("attn1.B_qkv"), w("attn1.A_o"), w("attn1.B_o")
             ns.A_q2, ns.sB_q2, ns.A_kv2, ns.sB_kv2 = w("attn2.A_q"), w("attn2.B_q"), w("attn2.A_kv"), w("attn2.B_kv")
@@ -443,38 +469,58 @@ class LoraState:
         self.kv_stacks = {C: (torch.empty(len(bl) * 2 * r, bl[0].A_kv2.shape[1], device=device, dtype=ELEM),
                               torch.empty(len(bl) * 2 * C, r, device=device, dtype=ELEM), bl)
                           for C, bl in by_c.items()}
-        self._b_views = [self.seg(self.work, p, k) for p, _, _ in blocks for k in self.layout[p] if ".B_" in k]
+        self._b_views = [self.seg(self.work, p, k, padded=True) for p, _, _ in blocks for k in self.layout[p]
+                         if ".B_" in k]
+        # r < 8: one descriptor per peft tensor (A then B of every adapter, in the flat buffers' block order, so a
+        # gradient unit's tensors are one range of the table) for the master -> working-copy pack and the gradient fold
+        self._pack = self._fold = None
+        self._fold_names, self._fold_units = [], {}
+        if self.grad_pad is not None and device.type == "cuda":
+            pack, fold = [], []
+            for name in self.adapter_names(layout_order=True):
+                views = zip(self.adapter_views(self.master, name), self.adapter_views(self.grad, name),
+                            self.adapter_views(self.work, name, padded=True),
+                            self.adapter_views(self.grad_pad, name, padded=True))
+                for j, (m, g, wp, gp) in enumerate(views):
+                    pack.append((m, wp, j == 1))  # B takes the alpha / r pre-scale
+                    fold.append((g, gp, False))
+                    self._fold_names.append(name)
+            self._pack = K.LoraPadTable(pack, device, ELEM)
+            self._fold = K.LoraPadTable(fold, device, torch.float32)
 
-    def seg(self, t, path, key):
-        off, rows, cols = self.layout[path][key]
+    def seg(self, t, path, key, padded=False):
+        off, rows, cols = (self.pad_layout if padded else self.layout)[path][key]
         return t[off:off + rows * cols].view(rows, cols)
 
-    # peft per-adapter views (A [r][in], B [out][r]) of a flat tensor
-    def adapter_views(self, t, name):
+    def adapter_views(self, t, name, padded=False):
+        """(A, B) of adapter `name` in the flat tensor t: peft's [r][in] / [out][r] in the logical layout (master,
+        grad), [r_pad][in] / [out][r_pad] in the padded one (work, grad_pad)."""
         path, attn, mod = name.rsplit(".", 2)[0], name.rsplit(".", 2)[1], name.rsplit(".", 2)[2]
         if mod == "0":  # to_out.0
             path, attn = name.rsplit(".", 3)[0], name.rsplit(".", 3)[1]
             mod = "to_out.0"
-        r = self.r
+        r = self.r_pad if padded else self.r
+        seg = lambda key: self.seg(t, path, key, padded)
         if attn == "attn1":
             if mod in ("to_q", "to_k", "to_v"):
                 j = ("to_q", "to_k", "to_v").index(mod)
-                A = self.seg(t, path, "attn1.A_qkv")[j * r:(j + 1) * r]
-                Bm = self.seg(t, path, "attn1.B_qkv")
+                A = seg("attn1.A_qkv")[j * r:(j + 1) * r]
+                Bm = seg("attn1.B_qkv")
                 C = Bm.shape[0] // 3
                 return A, Bm[j * C:(j + 1) * C]
-            return self.seg(t, path, "attn1.A_o"), self.seg(t, path, "attn1.B_o")
+            return seg("attn1.A_o"), seg("attn1.B_o")
         if mod == "to_q":
-            return self.seg(t, path, "attn2.A_q"), self.seg(t, path, "attn2.B_q")
+            return seg("attn2.A_q"), seg("attn2.B_q")
         if mod in ("to_k", "to_v"):
             j = ("to_k", "to_v").index(mod)
-            Bm = self.seg(t, path, "attn2.B_kv")
+            Bm = seg("attn2.B_kv")
             C = Bm.shape[0] // 2
-            return self.seg(t, path, "attn2.A_kv")[j * r:(j + 1) * r], Bm[j * C:(j + 1) * C]
-        return self.seg(t, path, "attn2.A_o"), self.seg(t, path, "attn2.B_o")
+            return seg("attn2.A_kv")[j * r:(j + 1) * r], Bm[j * C:(j + 1) * C]
+        return seg("attn2.A_o"), seg("attn2.B_o")
 
-    def adapter_names(self):
-        for path, _, _ in self.blocks:
+    def adapter_names(self, layout_order=False):
+        """Adapter module paths in forward order (layout_order: in the flat buffers' block order, the backward's)."""
+        for path, _, _ in (reversed(self.blocks) if layout_order else self.blocks):
             for a in ("attn1", "attn2"):
                 for m in ("to_q", "to_k", "to_v", "to_out.0"):
                     yield f"{path}.{a}.{m}"
@@ -492,20 +538,45 @@ class LoraState:
 
     def refresh(self, cast=True):
         """bf16 working copies (B pre-scaled by alpha/r) and their transposed forms after a master update (cast=False:
-        the optimizer already wrote work = bf16(master))."""
+        the optimizer already wrote work = bf16(master)).  r < 8: the working copies are the padded ones, always filled
+        here from the master by one pso_lora_pack launch (the same cast and pre-scale, zero pads)."""
         self.version = getattr(self, "version", 0) + 1  # keys the fp8 copies of the sB stacks (fp8 forward)
-        if cast:
-            K.cast_f32_bf16(self.master, out=self.work)
-        if self.scale != 1.0:
-            for Bw in self._b_views:
-                K.axpby(self.scale, Bw, out=Bw)
+        if self._pack is not None:
+            self._pack.pack(self.scale)
+        else:
+            if cast:
+                K.cast_f32_bf16(self.master, out=self.work)
+            if self.scale != 1.0:
+                for Bw in self._b_views:
+                    K.axpby(self.scale, Bw, out=Bw)
         self._transposes()
         for A, sB, bl in self.kv_stacks.values():
             torch.cat([L.A_kv2 for L in bl], 0, out=A)
             torch.cat([L.sB_kv2 for L in bl], 0, out=sB)
 
     def grad_seg(self, path, key):
+        """Where the backward's weight-gradient products of segment `key` accumulate: the flat gradient, or for r < 8
+        the padded scratch that fold_grads adds into it."""
+        if self.grad_pad is not None:
+            return self.seg(self.grad_pad, path, key, padded=True)
         return self.seg(self.grad, path, key)
+
+    def fold_range(self, unit):
+        """(first, count) of gradient unit `unit`'s records in the fold table; () when it holds no adapter (or the
+        rank needs no fold)."""
+        rng = self._fold_units.get(unit)
+        if rng is None:
+            idx = [i for i, nm in enumerate(self._fold_names) if nm.startswith(unit + ".")]
+            assert idx == list(range(idx[0], idx[0] + len(idx))) if idx else True, "a unit's adapters form one range"
+            rng = self._fold_units[unit] = (idx[0], len(idx)) if idx else ()
+        return rng
+
+    def fold_grads(self, unit):
+        """r < 8: grad += the logical part of grad_pad for the adapters of gradient unit `unit`, then that part of
+        grad_pad = 0 (one pso_lora_grad_fold launch on the current stream).  Nothing to do for other ranks / units."""
+        rng = self.fold_range(unit)
+        if rng:
+            self._fold.fold(*rng)
 
     def state_dict_peft(self):
         """{module_path.lora_A.weight, module_path.lora_B.weight} (get_peft_model_state_dict naming)."""
@@ -1376,7 +1447,7 @@ class UNet2DConditionModel(nn.Module):
         rt.kv_cache = {}
         rt.kv_text = lambda C: self.kv_text(rt, C)
         rt.lora = self.lora
-        rt.r = self.lora.r if lora_on else 0
+        rt.r = self.lora.r_pad if lora_on else 0  # the rank the kernels slice by (LoraState.r_pad)
         rt.fp8 = self._fp8_weight if self.fp8 else None
         return rt
 
@@ -1503,9 +1574,16 @@ class UNet2DConditionModel(nn.Module):
         dwq = K.TnRankQueue() if TN_BATCH else None
         rt.dw = dwq.add if dwq is not None else K.gemm_tn
 
+        lora = self.lora if rt.lora_on and self.lora.grad_pad is not None else None
+
         def done(unit):
             if dwq is not None:
                 dwq.flush()
+            if lora is not None and lora.fold_range(unit):
+                # r < 8: the unit's products went into the padded scratch as plain launches inside rt.side.launch
+                # (rank 8 is not a TN_RANKS width, so none was deferred); the fold follows them on the same stream,
+                # and unit_done's side.join() (GradBuckets._issue) then orders the all-reduce after it
+                rt.side.launch(lambda: lora.fold_grads(unit))
             unit_done(unit)
 
         done("conv_out")

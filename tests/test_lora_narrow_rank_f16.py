@@ -1,0 +1,34 @@
+"""The narrow LoRA ranks on the fp16 library: tests/test_gpu_lora_narrow_rank.py in one fresh PSO_LIB=f16 child
+process (the element type is per process), as tests/test_f16_build.py::test_f16_library_on_gpu runs the fp16 cases."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F16_LIB = os.path.join(ROOT, "pairwise_sample_optimization_amd", "libpso_amd_f16.so")
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_narrow_rank_cases_on_the_f16_library(cuda, capsys):
+    """-x, so a fault ends the child at once; the child's whole log goes to $PSO_TEST_LOG_DIR/f16_narrow_rank_child.log
+    when that variable names a directory (the failure message carries its tail either way).  The DreamBooth case
+    skips itself there: that trainer raises under the f16 library by design."""
+    assert os.path.exists(F16_LIB), "libpso_amd_f16.so not built (make -C pairwise_sample_optimization_amd/csrc)"
+    env = dict(os.environ, PSO_LIB="f16")
+    env.pop("PSO_LIB_PATH", None)
+    cmd = [sys.executable, "-u", "-m", "pytest", "-x", "-q", "-s", "-p", "no:cacheprovider", "--timeout", "300",
+           "--timeout-method", "thread", "-m", "gpu", os.path.join(ROOT, "tests", "test_gpu_lora_narrow_rank.py")]
+    r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=540)
+    tail = r.stdout[-6000:] + r.stderr[-2000:]
+    with capsys.disabled():  # the child's summary line belongs in the suite log
+        print("\n[f16 narrow-rank child] " + (r.stdout.strip().splitlines() or ["(no output)"])[-1], flush=True)
+    out_dir = os.environ.get("PSO_TEST_LOG_DIR", "")
+    if out_dir and os.path.isdir(out_dir):
+        with open(os.path.join(out_dir, "f16_narrow_rank_child.log"), "w") as f:
+            f.write(r.stdout + r.stderr)
+    assert r.returncode == 0, tail
+    assert " passed" in r.stdout and " failed" not in r.stdout and " error" not in r.stdout, tail
+    assert "1 skipped" in r.stdout, tail  # the DreamBooth case alone
