@@ -463,6 +463,58 @@ int pso_adamw8bit_step_blocks_zero_grad(long n, int nblk, const long* desc, floa
                                         float beta1, float beta2, float eps, float weight_decay, int step,
                                         float grad_scale, const float* clip_coef, void* stream);
 int pso_zero_f32(long n, float* x, void* stream);
+/* Device-resident dynamic loss scaling for fp16 training (torch.amp.GradScaler's state machine, T:303-319, 344-350,
+ * with its state on the device as GradScaler keeps it: no host read-back in an optimizer step, every entry below is
+ * capturable).  amp_state is a caller-owned block of PSO_AMP_WORDS four-byte words, 4-B aligned, that only these
+ * entries write (the caller initialises it with a copy from the host); word w holds
+ *   PSO_AMP_SCALE          f32  the loss scale S (a power of two with the default factors); pass its address as
+ *                               `grad_out` of pso_pair_loss_bwd / pso_db_loss_bwd so that backward runs on loss * S
+ *   PSO_AMP_INV_SCALE      f32  1 / S, kept in step with S
+ *   PSO_AMP_FOUND_INF      i32  1 when the last pso_amp_unscale_clip saw a non-finite norm, else 0
+ *   PSO_AMP_GROWTH_TRACKER i32  clean steps since the scale last changed
+ *   PSO_AMP_STEP           i32  applied optimizer steps (AdamW's `step`; a skipped step does not count)
+ *   PSO_AMP_SKIPPED        i32  optimizer steps skipped for a non-finite gradient
+ *   PSO_AMP_NORM           f32  last gradient norm (unscaled)          PSO_AMP_CLIP_COEF  f32  its clip coefficient
+ *   PSO_AMP_GRAD_MUL       f32  grad_scale / S of the last unscale: the factor the _amp steps put on the gradient
+ *   PSO_AMP_BC1, PSO_AMP_BC2_SQRT  f32  1 - b1^step, sqrt(1 - b2^step) in fp32 (pso_adamw_step's formulas)
+ *   PSO_AMP_C1, PSO_AMP_C2         f32  the same in double, rounded (the 8-bit step's c1 / c2)
+ *   the remaining words are reserved (zero).
+ * pso_amp_unscale_clip: norm = ||grad||_2 * grad_scale * (1 / S) -- pso_grad_clip_coef's expression with
+ *   grad_scale / S -- into NORM, CLIP_COEF and GRAD_MUL; FOUND_INF = !isfinite(norm); a finite norm advances STEP and
+ *   writes that step's BC1 .. C2.  ws as for pso_grad_clip_coef.
+ * pso_amp_update: FOUND_INF -> S *= backoff_factor, tracker = 0, SKIPPED += 1; otherwise tracker += 1 and, when it
+ *   reaches growth_interval, S *= growth_factor and tracker = 0 (GradScaler.update).
+ * pso_adamw_step_amp / pso_adamw8bit_step_blocks[_zero_grad]_amp: the steps above on grad * GRAD_MUL * CLIP_COEF with
+ *   the bias corrections of STEP, all read from the state.  FOUND_INF: parameters, moments / codes / absmax / 32-bit
+ *   state and the 16-bit working copy are left untouched; the zero_grad form still zeroes the gradient it covers. */
+#define PSO_AMP_WORDS 16
+#define PSO_AMP_SCALE 0
+#define PSO_AMP_INV_SCALE 1
+#define PSO_AMP_FOUND_INF 2
+#define PSO_AMP_GROWTH_TRACKER 3
+#define PSO_AMP_STEP 4
+#define PSO_AMP_SKIPPED 5
+#define PSO_AMP_NORM 6
+#define PSO_AMP_CLIP_COEF 7
+#define PSO_AMP_GRAD_MUL 8
+#define PSO_AMP_BC1 9
+#define PSO_AMP_BC2_SQRT 10
+#define PSO_AMP_C1 11
+#define PSO_AMP_C2 12
+int pso_amp_unscale_clip(long n, const float* grad, float grad_scale, float max_norm, float beta1, float beta2,
+                         void* amp_state, void* ws, size_t ws_bytes, void* stream);
+int pso_amp_update(void* amp_state, float growth_factor, float backoff_factor, int growth_interval, void* stream);
+int pso_adamw_step_amp(long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, const void* amp_state, void* stream);
+int pso_adamw8bit_step_blocks_amp(long n, int nblk, const long* desc, float* param, void* param_bf16,
+                                  const float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
+                                  float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, float lr, float beta1,
+                                  float beta2, float eps, float weight_decay, const void* amp_state, void* stream);
+int pso_adamw8bit_step_blocks_zero_grad_amp(long n, int nblk, const long* desc, float* param, void* param_bf16,
+                                            float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
+                                            float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, float lr,
+                                            float beta1, float beta2, float eps, float weight_decay,
+                                            const void* amp_state, void* stream);
 int pso_preference(int P, int m, const float* rewards, const int64_t* reward_idx, int mode, float* pref,
                    void* stream);
 

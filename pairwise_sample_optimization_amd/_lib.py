@@ -31,6 +31,11 @@ MODE_DMD = 1
 MODE_DMD_F16 = 2   # DMD2 latent-dtype replay modes (include/pso_amd.h PSO_MODE_DMD_F16 / _BF16)
 MODE_DMD_BF16 = 3
 COEF_STRIDE = 8
+# words of the device loss-scaler state (include/pso_amd.h PSO_AMP_*): floats and int32 counters, 4 bytes each
+AMP_WORDS = 16
+(AMP_SCALE, AMP_INV_SCALE, AMP_FOUND_INF, AMP_GROWTH_TRACKER, AMP_STEP, AMP_SKIPPED, AMP_NORM, AMP_CLIP_COEF,
+ AMP_GRAD_MUL, AMP_BC1, AMP_BC2_SQRT, AMP_C1, AMP_C2) = range(13)
+AMP_INT_WORDS = (AMP_FOUND_INF, AMP_GROWTH_TRACKER, AMP_STEP, AMP_SKIPPED)
 
 _lib = None
 
@@ -143,6 +148,13 @@ SIGNATURES = {
                                        vp, vp]),
     "pso_adamw8bit_step_blocks_zero_grad": (ci, [cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf,
                                                  ci, cf, vp, vp]),
+    "pso_amp_unscale_clip": (ci, [cl, vp, cf, cf, cf, cf, vp, vp, csz, vp]),
+    "pso_amp_update": (ci, [vp, cf, cf, ci, vp]),
+    "pso_adamw_step_amp": (ci, [cl, vp, vp, vp, vp, cf, cf, cf, cf, cf, vp, vp]),
+    "pso_adamw8bit_step_blocks_amp": (ci, [cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, vp,
+                                           vp]),
+    "pso_adamw8bit_step_blocks_zero_grad_amp": (ci, [cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf,
+                                                     cf, vp, vp]),
     "pso_zero_f32": (ci, [cl, vp, vp]),
     "pso_preference": (ci, [ci, ci, vp, vp, ci, vp, vp]),
     "pso_nhwc_to_nchw": (ci, [ci, ci, cl, vp, vp, ci, vp]),

@@ -46,34 +46,97 @@ __global__ void sqnorm_partial_kernel(long n, const float* __restrict__ g, doubl
   }
 }
 
-// out[0] = ||g * scale||_2, out[1] = clip coefficient (1 if max_norm <= 0)
-__global__ void clip_coef_kernel(int nparts, const double* __restrict__ part, float scale, float max_norm,
-                                 float* __restrict__ out) {
-  // one workgroup sums the per-block partials (fixed order: strided per thread, then wave and workgroup trees)
+// one workgroup sums the per-block partials (fixed order: strided per thread, then wave and workgroup trees); the sum
+// is valid in thread 0
+__device__ __forceinline__ double sum_partials(int nparts, const double* __restrict__ part) {
   __shared__ double red[OPT_THREADS / 64];
   double acc = 0.0;
   for (int i = threadIdx.x; i < nparts; i += blockDim.x) acc += part[i];
   acc = warp_sum_d(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
+  double s = 0.0;
+  if (threadIdx.x == 0)
     for (int w = 0; w < OPT_THREADS / 64; ++w) s += red[w];
+  return s;
+}
+
+// clip_grad_norm_'s coefficient (1 if max_norm <= 0; NaN for a NaN norm)
+__device__ __forceinline__ float clip_coef_of(float norm, float max_norm) {
+  float c = 1.0f;
+  if (max_norm > 0.f) {
+    c = max_norm / (norm + 1e-6f);
+    if (c > 1.0f) c = 1.0f;
+  }
+  return c;
+}
+
+// out[0] = ||g * scale||_2, out[1] = clip coefficient (1 if max_norm <= 0)
+__global__ void clip_coef_kernel(int nparts, const double* __restrict__ part, float scale, float max_norm,
+                                 float* __restrict__ out) {
+  const double s = sum_partials(nparts, part);
+  if (threadIdx.x == 0) {
     const float norm = (float)sqrt(s) * scale;
     out[0] = norm;
-    float c = 1.0f;
-    if (max_norm > 0.f) {
-      c = max_norm / (norm + 1e-6f);
-      if (c > 1.0f) c = 1.0f;
-    }
-    out[1] = c;
+    out[1] = clip_coef_of(norm, max_norm);
   }
 }
 
-__global__ void adamw_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                             float* __restrict__ v, float lr, float b1, float b2, float eps, float wd, float bc1,
-                             float bc2_sqrt, float gscale, const float* __restrict__ clip) {
-  const float s = gscale * (clip ? clip[1] : 1.0f);
+// ---- device-resident loss-scaler state (fp16 training; include/pso_amd.h PSO_AMP_*): 16 four-byte words, floats and
+// int32 counters side by side, read and written by the kernels below only (plain vector loads / stores, one thread)
+#define AMP_I(st, w) (reinterpret_cast<int*>(st)[w])
+#define AMP_CI(st, w) (reinterpret_cast<const int*>(st)[w])
+
+// unscale + norm + clip of the all-reduced gradient: the same fp32 expression as clip_coef_kernel with
+// scale = grad_scale / S (S a power of two: the product grad_scale * inv_scale is that quotient exactly).  A finite
+// norm advances the applied-step count and leaves that step's bias-correction constants in the state: bc1 / bc2_sqrt
+// by pso_adamw_step's fp32 formulas, c1 / c2 by adam8_launch's double ones.
+__global__ void amp_unscale_clip_kernel(int nparts, const double* __restrict__ part, float grad_scale, float max_norm,
+                                        float beta1, float beta2, float* __restrict__ st) {
+  const double s = sum_partials(nparts, part);
+  if (threadIdx.x == 0) {
+    const float mul = grad_scale * st[PSO_AMP_INV_SCALE];
+    const float norm = (float)sqrt(s) * mul;
+    const bool inf = !isfinite(norm);
+    st[PSO_AMP_NORM] = norm;
+    st[PSO_AMP_CLIP_COEF] = clip_coef_of(norm, max_norm);
+    st[PSO_AMP_GRAD_MUL] = mul;
+    AMP_I(st, PSO_AMP_FOUND_INF) = inf ? 1 : 0;
+    if (!inf) {
+      const int step = AMP_I(st, PSO_AMP_STEP) + 1;
+      AMP_I(st, PSO_AMP_STEP) = step;
+      st[PSO_AMP_BC1] = 1.0f - powf(beta1, (float)step);
+      st[PSO_AMP_BC2_SQRT] = sqrtf(1.0f - powf(beta2, (float)step));
+      const double b1 = beta1, b2 = beta2;
+      st[PSO_AMP_C1] = (float)(1.0 - pow(b1, (double)step));
+      st[PSO_AMP_C2] = (float)sqrt(1.0 - pow(b2, (double)step));
+    }
+  }
+}
+
+// amp.LossScaler.update (torch's GradScaler.update) on the state: back off after a skipped step, otherwise count
+// towards growth and grow after `interval` clean steps in a row
+__global__ void amp_update_kernel(float* __restrict__ st, float growth, float backoff, int interval) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  float scale = st[PSO_AMP_SCALE];
+  int tracker = AMP_I(st, PSO_AMP_GROWTH_TRACKER);
+  if (AMP_I(st, PSO_AMP_FOUND_INF)) {
+    scale *= backoff;
+    tracker = 0;
+    AMP_I(st, PSO_AMP_SKIPPED) += 1;
+  } else if (++tracker == interval) {
+    scale *= growth;
+    tracker = 0;
+  }
+  AMP_I(st, PSO_AMP_GROWTH_TRACKER) = tracker;
+  st[PSO_AMP_SCALE] = scale;
+  st[PSO_AMP_INV_SCALE] = 1.0f / scale;
+}
+
+// s = the factor on the gradient read (1/world, 1/loss-scale and the clip coefficient folded together)
+__device__ __forceinline__ void adamw_body(long n, float* __restrict__ p, const float* __restrict__ g,
+                                           float* __restrict__ m, float* __restrict__ v, float lr, float b1, float b2,
+                                           float eps, float wd, float bc1, float bc2_sqrt, float s) {
   const float step = lr / bc1;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const float gi = g[i] * s;
@@ -86,6 +149,21 @@ __global__ void adamw_kernel(long n, float* __restrict__ p, const float* __restr
     pi -= step * (mi / denom);
     p[i] = pi;
   }
+}
+
+__global__ void adamw_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                             float* __restrict__ v, float lr, float b1, float b2, float eps, float wd, float bc1,
+                             float bc2_sqrt, float gscale, const float* __restrict__ clip) {
+  adamw_body(n, p, g, m, v, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale * (clip ? clip[1] : 1.0f));
+}
+
+// the same step with the gradient factor, the bias corrections and the inf-skip read from the loss-scaler state
+__global__ void adamw_amp_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                 float* __restrict__ v, float lr, float b1, float b2, float eps, float wd,
+                                 const float* __restrict__ st) {
+  if (AMP_CI(st, PSO_AMP_FOUND_INF)) return;  // skipped step: parameters and moments untouched
+  adamw_body(n, p, g, m, v, lr, b1, b2, eps, wd, st[PSO_AMP_BC1], st[PSO_AMP_BC2_SQRT],
+             st[PSO_AMP_GRAD_MUL] * st[PSO_AMP_CLIP_COEF]);
 }
 
 // ---- blockwise 8-bit AdamW (bitsandbytes AdamW8bit: the reference default, config_sdxl_turbo_dpo.py:86, T:427-435)
@@ -145,12 +223,14 @@ __device__ __forceinline__ int adam8_node(int i) {
 // LAY = element-to-thread mapping inside a block.  0: thread t owns the 8 consecutive elements 8t .. 8t + 7 (each
 // 16-B access instruction of a wave spans 2 KB with 16-B gaps); 1: thread t owns 4t .. 4t + 3 and 1024 + 4t .. +3, so
 // every access instruction of a wave covers one contiguous range.  Per-block results are the same bits either way.
+// s = the factor on the gradient read.  The body of adamw8bit_kernel (host arguments) and adamw8bit_amp_kernel (the
+// loss-scaler state's).
 template <int LAY>
-__global__ __launch_bounds__(256) void adamw8bit_kernel(
+__device__ __forceinline__ void adamw8bit_body(
     long n, float* __restrict__ p, float* g, uint8_t* __restrict__ qm, uint8_t* __restrict__ qv,
     float* __restrict__ am, float* __restrict__ av, float b1, float omb1, float b2, float omb2, float eps_c2,
-    float step_size, float decay, float gscale, const float* __restrict__ clip, bf16_t* __restrict__ pw,
-    const long* __restrict__ desc, float* __restrict__ m32, float* __restrict__ v32, int zero_grad, Adam8Maps maps) {
+    float step_size, float decay, float s, bf16_t* __restrict__ pw, const long* __restrict__ desc,
+    float* __restrict__ m32, float* __restrict__ v32, int zero_grad, const Adam8Maps& maps) {
 #pragma clang fp contract(off)
   __shared__ float cs[256], cu[256], ts[256], tu[256];
   __shared__ float red[2][4];
@@ -177,7 +257,6 @@ __global__ __launch_bounds__(256) void adamw8bit_kernel(
   auto at = [&](int e) { return (e < 4 ? o0 : o1) + (e & 3); };
   // 16-B / 4-B vector accesses wherever both chunks are whole and aligned
   const bool full = o0 + 4 <= end && o1 + 4 <= end && (base & 3) == 0 && (!st32 || (soff & 3) == 0);
-  const float s = gscale * (clip ? clip[1] : 1.0f);
   float gv[8], pv[8];
   if (full) {
     const float4 g0 = *reinterpret_cast<const float4*>(g + o0), g1 = *reinterpret_cast<const float4*>(g + o1);
@@ -309,6 +388,39 @@ __global__ __launch_bounds__(256) void adamw8bit_kernel(
   if (t == 0) { am[blk] = nm; av[blk] = nv; }
 }
 
+template <int LAY>
+__global__ __launch_bounds__(256) void adamw8bit_kernel(
+    long n, float* __restrict__ p, float* g, uint8_t* __restrict__ qm, uint8_t* __restrict__ qv,
+    float* __restrict__ am, float* __restrict__ av, float b1, float omb1, float b2, float omb2, float eps_c2,
+    float step_size, float decay, float gscale, const float* __restrict__ clip, bf16_t* __restrict__ pw,
+    const long* __restrict__ desc, float* __restrict__ m32, float* __restrict__ v32, int zero_grad, Adam8Maps maps) {
+  adamw8bit_body<LAY>(n, p, g, qm, qv, am, av, b1, omb1, b2, omb2, eps_c2, step_size, decay,
+                      gscale * (clip ? clip[1] : 1.0f), pw, desc, m32, v32, zero_grad, maps);
+}
+
+// the per-tensor step with the gradient factor, c1 / c2 and the inf-skip read from the loss-scaler state.  A skipped
+// step leaves the parameters, codes, absmax, 32-bit state and working copy untouched; with zero_grad it still zeroes
+// the gradient elements its blocks cover (the host path zeroes the gradient of a skipped step too).
+template <int LAY>
+__global__ __launch_bounds__(256) void adamw8bit_amp_kernel(
+    long n, float* __restrict__ p, float* g, uint8_t* __restrict__ qm, uint8_t* __restrict__ qv,
+    float* __restrict__ am, float* __restrict__ av, float b1, float omb1, float b2, float omb2, float eps, float lr,
+    float decay, const float* __restrict__ st, bf16_t* __restrict__ pw, const long* __restrict__ desc,
+    float* __restrict__ m32, float* __restrict__ v32, int zero_grad, Adam8Maps maps) {
+#pragma clang fp contract(off)
+  if (AMP_CI(st, PSO_AMP_FOUND_INF)) {
+    if (zero_grad) {
+      const long base = desc[4 * (long)blockIdx.x], end = base + desc[4 * (long)blockIdx.x + 1];
+      for (long i = base + threadIdx.x; i < end; i += blockDim.x) g[i] = 0.f;
+    }
+    return;
+  }
+  const float c1 = st[PSO_AMP_C1], c2 = st[PSO_AMP_C2];
+  const float step_size = (-lr) * c2 / c1;  // adam8_launch's host expressions, in fp32 as there
+  adamw8bit_body<LAY>(n, p, g, qm, qv, am, av, b1, omb1, b2, omb2, c2 * eps, step_size, decay,
+                      st[PSO_AMP_GRAD_MUL] * st[PSO_AMP_CLIP_COEF], pw, desc, m32, v32, zero_grad, maps);
+}
+
 // bitsandbytes.functional.create_dynamic_map(signed, max_exponent_bits = 7, total_bits = 8), float32 like the
 // torch original (numpy-style linspace in double, cast to float32)
 static void adam8_dynamic_map(bool sgn, float* out) {
@@ -396,6 +508,37 @@ int pso_adamw_step(long n, float* param, const float* grad, float* exp_avg, floa
   return pso_check_launch("pso_adamw_step");
 }
 
+int pso_amp_unscale_clip(long n, const float* grad, float grad_scale, float max_norm, float beta1, float beta2,
+                         void* amp_state, void* ws, size_t ws_bytes, void* stream) {
+  PSO_ARG_CHECK(grad && amp_state && ws && ws_bytes >= pso_grad_clip_ws_bytes(n) && ((uintptr_t)amp_state & 3) == 0,
+                "pso_amp_unscale_clip: bad args");
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = nblocks(n);
+  sqnorm_partial_kernel<<<nb, OPT_THREADS, 0, st>>>(n, grad, (double*)ws);
+  amp_unscale_clip_kernel<<<1, OPT_THREADS, 0, st>>>(nb, (const double*)ws, grad_scale, max_norm, beta1, beta2,
+                                                    (float*)amp_state);
+  return pso_check_launch("pso_amp_unscale_clip");
+}
+
+int pso_amp_update(void* amp_state, float growth_factor, float backoff_factor, int growth_interval, void* stream) {
+  PSO_ARG_CHECK(amp_state && ((uintptr_t)amp_state & 3) == 0 && growth_factor > 1.0f && backoff_factor > 0.0f &&
+                    backoff_factor < 1.0f && growth_interval >= 1,
+                "pso_amp_update: bad args");
+  amp_update_kernel<<<1, 64, 0, (hipStream_t)stream>>>((float*)amp_state, growth_factor, backoff_factor,
+                                                      growth_interval);
+  return pso_check_launch("pso_amp_update");
+}
+
+int pso_adamw_step_amp(long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, const void* amp_state, void* stream) {
+  PSO_ARG_CHECK(param && grad && exp_avg && exp_avg_sq && amp_state && ((uintptr_t)amp_state & 3) == 0,
+                "pso_adamw_step_amp: bad args");
+  adamw_amp_kernel<<<nblocks(n), OPT_THREADS, 0, (hipStream_t)stream>>>(n, param, grad, exp_avg, exp_avg_sq, lr,
+                                                                        beta1, beta2, eps, weight_decay,
+                                                                        (const float*)amp_state);
+  return pso_check_launch("pso_adamw_step_amp");
+}
+
 size_t pso_adamw8bit_blocks(long n) { return (size_t)((n + ADAM8_BLOCK - 1) / ADAM8_BLOCK); }
 
 void pso_adamw8bit_maps(float* signed_map, float* unsigned_map) {
@@ -406,13 +549,15 @@ void pso_adamw8bit_maps(float* signed_map, float* unsigned_map) {
 static int adam8_launch(long n, int nblk, float* param, void* param_bf16, float* grad, int zero_grad, uint8_t* exp_avg_q,
                         uint8_t* exp_avg_sq_q, float* absmax_m, float* absmax_v, const long* desc, float* m32,
                         float* v32, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                        float grad_scale, const float* clip_coef, void* stream) {
+                        float grad_scale, const float* clip_coef, void* stream, const float* amp = nullptr) {
   static Adam8Maps maps = [] {
     Adam8Maps m;
     adam8_dynamic_map(true, m.s);
     adam8_dynamic_map(false, m.u);
     return m;
   }();
+  // amp != nullptr: step, grad_scale and clip_coef are unused -- c1 / c2, the gradient factor and the inf-skip come
+  // from the loss-scaler state on the device (adamw8bit_amp_kernel)
   const double b1 = beta1, b2 = beta2;
   const float c1 = (float)(1.0 - std::pow(b1, step));
   const float c2 = (float)std::sqrt(1.0 - std::pow(b2, step));
@@ -433,6 +578,14 @@ static int adam8_launch(long n, int nblk, float* param, void* param_bf16, float*
 #define PSO_ADAM8_ARGS                                                                                                   \
   n, param, grad, exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, beta1, omb1, beta2, omb2, c2 * eps, step_size, decay,     \
       grad_scale, clip_coef, (bf16_t*)param_bf16, desc, m32, v32, zero_grad, maps
+#define PSO_ADAM8_AMP_ARGS                                                                                               \
+  n, param, grad, exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, beta1, omb1, beta2, omb2, eps, lr, decay, amp,            \
+      (bf16_t*)param_bf16, desc, m32, v32, zero_grad, maps
+  if (amp) {
+    adamw8bit_amp_kernel<ADAM8_LAYOUT_DEFAULT><<<nblk, 256, 0, st>>>(PSO_ADAM8_AMP_ARGS);
+    return pso_check_launch("pso_adamw8bit_step_amp");
+  }
+#undef PSO_ADAM8_AMP_ARGS
 #ifdef PSO_BENCH_KNOBS
   if (lay)
     adamw8bit_kernel<1><<<nblk, 256, 0, st>>>(PSO_ADAM8_ARGS);
@@ -462,7 +615,7 @@ static int adam8_blocks(const char* who, long n, int nblk, const long* desc, flo
                         float* grad, int zero_grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
                         float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, float lr, float beta1, float beta2,
                         float eps, float weight_decay, int step, float grad_scale, const float* clip_coef,
-                        void* stream) {
+                        void* stream, const float* amp = nullptr) {
   PSO_ARG_CHECK(param && grad && exp_avg_q && exp_avg_sq_q && absmax_m && absmax_v && step >= 1 && n > 0 &&
                     nblk >= 0 && (nblk == 0 || desc),
                 "%s: bad args", who);
@@ -471,7 +624,7 @@ static int adam8_blocks(const char* who, long n, int nblk, const long* desc, flo
                 "%s: param / grad / param_bf16 / 32-bit state need 16-B, the code arrays 8-B alignment", who);
   return adam8_launch(n, nblk, param, param_bf16, grad, zero_grad, exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, desc,
                       exp_avg_32, exp_avg_sq_32, lr, beta1, beta2, eps, weight_decay, step, grad_scale, clip_coef,
-                      stream);
+                      stream, amp);
 }
 
 int pso_adamw8bit_step_blocks(long n, int nblk, const long* desc, float* param, void* param_bf16, const float* grad,
@@ -491,6 +644,27 @@ int pso_adamw8bit_step_blocks_zero_grad(long n, int nblk, const long* desc, floa
   return adam8_blocks("pso_adamw8bit_step_blocks_zero_grad", n, nblk, desc, param, param_bf16, grad, 1, exp_avg_q,
                       exp_avg_sq_q, absmax_m, absmax_v, exp_avg_32, exp_avg_sq_32, lr, beta1, beta2, eps,
                       weight_decay, step, grad_scale, clip_coef, stream);
+}
+
+int pso_adamw8bit_step_blocks_amp(long n, int nblk, const long* desc, float* param, void* param_bf16,
+                                  const float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
+                                  float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, float lr, float beta1,
+                                  float beta2, float eps, float weight_decay, const void* amp_state, void* stream) {
+  PSO_ARG_CHECK(amp_state && ((uintptr_t)amp_state & 3) == 0, "pso_adamw8bit_step_blocks_amp: no amp_state");
+  return adam8_blocks("pso_adamw8bit_step_blocks_amp", n, nblk, desc, param, param_bf16, const_cast<float*>(grad), 0,
+                      exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, exp_avg_32, exp_avg_sq_32, lr, beta1, beta2, eps,
+                      weight_decay, 1, 1.0f, nullptr, stream, (const float*)amp_state);
+}
+
+int pso_adamw8bit_step_blocks_zero_grad_amp(long n, int nblk, const long* desc, float* param, void* param_bf16,
+                                            float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
+                                            float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, float lr,
+                                            float beta1, float beta2, float eps, float weight_decay,
+                                            const void* amp_state, void* stream) {
+  PSO_ARG_CHECK(amp_state && ((uintptr_t)amp_state & 3) == 0, "pso_adamw8bit_step_blocks_zero_grad_amp: no amp_state");
+  return adam8_blocks("pso_adamw8bit_step_blocks_zero_grad_amp", n, nblk, desc, param, param_bf16, grad, 1, exp_avg_q,
+                      exp_avg_sq_q, absmax_m, absmax_v, exp_avg_32, exp_avg_sq_32, lr, beta1, beta2, eps,
+                      weight_decay, 1, 1.0f, nullptr, stream, (const float*)amp_state);
 }
 
 int pso_adamw8bit_step(long n, float* param, const float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q,

@@ -14,26 +14,43 @@ personalization/scripts/pso_dog.sh (EDM-style epsilon training, loss "pso_db", b
 
 Here the VAE encoder, the UNet forward/backward and the loss all run on libpso_amd; for loss_type "pso" the reference
 eps (adapters disabled, DB:1894-1920) comes from the same paired UNet pass as the policy eps.  No host sync.
+
+Under the f16 library (the recipes' own --mixed_precision="fp16") the trainer needs a loss scaler (loss_scale=): the
+backward runs on loss * S / gas and the shared optimizer step unscales, skips a non-finite step and backs the scale
+off.  The front end is fp32 in the reference as well: the recipes name a VAE, so the latents are not cast to the
+weight dtype (DB:1754-1755) and the VAE stays fp32 (DB:1293); noise, add_noise, the sigmas and the EDM
+preconditioning are fp32 -- what prepare_inputs and db_loss.hip compute.
 """
 
 import torch
 
 from . import _lib
 from . import kernels as K
+from .amp import DeviceLossScaler, LossScaler, make_scaler
 from .schedulers import EulerDiscreteScheduler, db_distill_timesteps
-from .trainer import lora_optimizer_step
-
+from .trainer import OptStep, lora_optimizer_step, trainable_segments
 
 
 class DreamBoothPSOTrainer:
+    opt_step = OptStep()
+
     def __init__(self, unet, vae, loss_type="pso_db", beta_pso=5.0, neg_defactor=0.1, prior_loss_weight=0.5,
                  distill_train_timesteps=4, learning_rate=2e-4, betas=(0.9, 0.999), adam_weight_decay=1e-4,
-                 adam_epsilon=1e-8, max_grad_norm=1.0, gradient_accumulation_steps=4, process_group=None):
-        """Defaults: DB argparse defaults (DB:636-674, 757-777) overridden by the recipe scripts/pso_dog.sh."""
+                 adam_epsilon=1e-8, max_grad_norm=1.0, gradient_accumulation_steps=4, process_group=None,
+                 loss_scale=None, use_8bit_adam=False):
+        """Defaults: DB argparse defaults (DB:636-674, 757-777) overridden by the recipe scripts/pso_dog.sh.
+        loss_scale: None | float (initial scale) | amp.LossScaler | amp.DeviceLossScaler -- fp16 training under the
+        f16 library, which refuses to train without one; the bf16 library takes none.  use_8bit_adam: the script's
+        --use_8bit_adam (DB:630), the blockwise 8-bit AdamW as in PSOTrainer."""
         if loss_type not in ("pso", "pso_db"):
             raise ValueError(f"Unknown loss type {loss_type}")  # DB:1929
-        # this trainer has no loss scaler: under the f16 library it would train fp16 without one
-        _lib.require_bf16("DreamBooth PSO training (DreamBoothPSOTrainer)")
+        self.scaler = make_scaler(loss_scale)
+        if self.scaler is None:
+            # without a loss scaler the f16 library would train fp16 unscaled
+            _lib.require_bf16("DreamBooth PSO training (DreamBoothPSOTrainer) without loss_scale=")
+        elif _lib.ELEM_DTYPE != torch.float16:
+            raise ValueError("loss_scale is for fp16 training (PSO_LIB=f16, libpso_amd_f16.so); the loaded library "
+                             f"computes in {_lib.ELEM_DTYPE}")
         self.unet, self.vae = unet, vae
         self.loss_type = loss_type
         self.lt = K.DB_SIGMOID if loss_type == "pso" else K.DB_HINGE
@@ -45,13 +62,67 @@ class DreamBoothPSOTrainer:
         self.pg = process_group
         self.sched = EulerDiscreteScheduler()
         st = unet.lora
-        self.exp_avg = torch.zeros_like(st.master)
-        self.exp_avg_sq = torch.zeros_like(st.master)
+        self.adam8 = K.Adam8State(st.master.numel(), st.master.device, segments=trainable_segments(unet)) \
+            if use_8bit_adam else None
+        self.exp_avg = None if use_8bit_adam else torch.zeros_like(st.master)
+        self.exp_avg_sq = None if use_8bit_adam else torch.zeros_like(st.master)
         self.clip_buf = torch.zeros(2, device=st.master.device, dtype=torch.float32)
         self.opt_step = 0
         self.n_micro = 0
         self.loss_hist = []
         self.auto_step = True
+
+    @classmethod
+    def from_args(cls, unet, vae, args, process_group=None, loss_scale=None):
+        """Build from the reference script's argparse namespace (DB:parse_args).  Read: loss_type, beta_pso,
+        neg_defactor, prior_loss_weight, distill_train_timesteps, learning_rate, adam_beta1 / adam_beta2 /
+        adam_weight_decay / adam_epsilon, max_grad_norm, gradient_accumulation_steps, use_8bit_adam, mixed_precision;
+        a field the namespace does not carry counts as the script's default.  Flags that ask for training this
+        trainer does not implement raise ValueError naming the flag (unet.check_lora_config's rule) instead of
+        training something else.
+        Precision: the f16 library runs mixed_precision="fp16" only and trains with `loss_scale` (default: a host
+        amp.LossScaler()); the bf16 library keeps its documented substitute -- bf16 arithmetic, no scaler -- whatever
+        mixed_precision says."""
+        def get(name, default):
+            return getattr(args, name, default)
+
+        if str(get("optimizer", "AdamW")).lower() != "adamw":
+            raise ValueError(f"--optimizer={get('optimizer', None)!r} is not implemented (AdamW only; DB:623-627)")
+        for flag in ("train_text_encoder", "with_prior_preservation", "use_dora"):
+            if get(flag, False):
+                raise ValueError(f"--{flag} is not implemented (the recipes under personalization/scripts leave it off)")
+        if not get("do_edm_style_training", False):
+            raise ValueError("--do_edm_style_training is required: only the EDM-style epsilon training of the recipes "
+                             "(DB:1787-1796) is implemented")
+        sched = get("lr_scheduler", "constant")
+        if sched != "constant":
+            raise ValueError(f"--lr_scheduler={sched!r} is not implemented (constant only)")
+        if get("lr_warmup_steps", 500) != 0:
+            raise ValueError(f"--lr_warmup_steps={get('lr_warmup_steps', 500)!r} is not implemented: the constant "
+                             "schedule here has no warm-up (the recipes pass 0)")
+        mp = get("mixed_precision", None)
+        if _lib.ELEM_DTYPE == torch.float16:
+            if mp != "fp16":
+                raise ValueError(f"the f16 library (PSO_LIB=f16) trains --mixed_precision=fp16 only, got {mp!r}: "
+                                 "unset PSO_LIB for the bf16 library")
+            if loss_scale is None:
+                loss_scale = LossScaler()
+        elif loss_scale is not None:
+            raise ValueError("loss_scale is for fp16 training (PSO_LIB=f16, libpso_amd_f16.so); the loaded library "
+                             f"computes in {_lib.ELEM_DTYPE}")
+        return cls(unet, vae, loss_type=get("loss_type", "sigmoid"), beta_pso=get("beta_pso", 200),
+                   neg_defactor=get("neg_defactor", 0.1), prior_loss_weight=get("prior_loss_weight", 1.0),
+                   distill_train_timesteps=get("distill_train_timesteps", 4),
+                   learning_rate=get("learning_rate", 1e-4), betas=(get("adam_beta1", 0.9), get("adam_beta2", 0.999)),
+                   adam_weight_decay=get("adam_weight_decay", 1e-4), adam_epsilon=get("adam_epsilon", 1e-8),
+                   max_grad_norm=get("max_grad_norm", 1.0),
+                   gradient_accumulation_steps=get("gradient_accumulation_steps", 1), process_group=process_group,
+                   loss_scale=loss_scale, use_8bit_adam=bool(get("use_8bit_adam", False)))
+
+    @property
+    def loss_scale(self):
+        """The factor on the loss in backward (1.0 without a scaler); with a DeviceLossScaler this reads the device."""
+        return 1.0 if self.scaler is None else self.scaler.scale
 
     def prepare_inputs(self, pixel_values, generator=None):
         """DB:1731-1796 on device: latents, shared noise, distilled timesteps, EDM-preconditioned UNet input.
@@ -91,8 +162,12 @@ class DreamBoothPSOTrainer:
         loss, _, _ = K.db_loss_fwd(self.lt, eps_pol, inp["noisy"], inp["x0"], inp["sigma"], self.beta, self.nd,
                                    self.prior_w, ws, eps_ref=eps_ref)
         # accelerator.backward divides by gradient_accumulation_steps
-        deps = K.db_loss_bwd(self.lt, eps_pol, inp["noisy"], inp["x0"], inp["sigma"], self.beta, self.nd,
-                             self.prior_w, ws, grad_scale=1.0 / self.gas)
+        if isinstance(self.scaler, DeviceLossScaler):  # loss * S / gas, S read on the device
+            deps = K.db_loss_bwd(self.lt, eps_pol, inp["noisy"], inp["x0"], inp["sigma"], self.beta, self.nd,
+                                 self.prior_w, ws, grad_out=self.scaler.scale_word, grad_scale=1.0 / self.gas)
+        else:
+            deps = K.db_loss_bwd(self.lt, eps_pol, inp["noisy"], inp["x0"], inp["sigma"], self.beta, self.nd,
+                                 self.prior_w, ws, grad_scale=1.0 / self.gas * self.loss_scale)
         u.backward_nhwc(deps, rt)
         self.loss_hist.append(loss)
         self.n_micro += 1

@@ -1060,6 +1060,59 @@ def adamw8bit_step(param, grad, state, lr, betas, eps, weight_decay, step, grad_
     return False
 
 
+# ---- device-resident loss scaling (amp.DeviceLossScaler): `amp_state` is its int32 [AMP_WORDS] state tensor ----------
+def _check_amp_state(amp_state):
+    require_cuda(amp_state)
+    if amp_state.dtype != torch.int32 or amp_state.numel() != _lib.AMP_WORDS or not amp_state.is_contiguous():
+        raise _lib.PsoLibError(f"loss-scaler state must be a contiguous int32 [{_lib.AMP_WORDS}] device tensor")
+
+
+def amp_unscale_clip(grad, max_norm, amp_state, betas, grad_scale=1.0):
+    """Norm and clip coefficient of grad * grad_scale / S into the state, found_inf from the norm, and -- when it is
+    finite -- the next step count with its bias corrections.  No read-back."""
+    require_cuda(grad)
+    _check_amp_state(amp_state)
+    n = grad.numel()
+    wsb = lib().pso_grad_clip_ws_bytes(n)
+    ws = torch.empty(wsb, device=grad.device, dtype=torch.uint8)
+    check(lib().pso_amp_unscale_clip(n, ptr(grad), float(grad_scale), float(max_norm), float(betas[0]),
+                                     float(betas[1]), ptr(amp_state), ptr(ws), wsb, stream_ptr()),
+          "pso_amp_unscale_clip")
+
+
+def amp_update(amp_state, growth_factor, backoff_factor, growth_interval):
+    """amp.LossScaler.update on the device state, driven by its found_inf word."""
+    _check_amp_state(amp_state)
+    check(lib().pso_amp_update(ptr(amp_state), float(growth_factor), float(backoff_factor), int(growth_interval),
+                               stream_ptr()), "pso_amp_update")
+
+
+def adamw_step_amp(param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, amp_state):
+    """adamw_step with the gradient factor, the step's bias corrections and the inf-skip read from the state."""
+    require_cuda(param, grad, exp_avg, exp_avg_sq)
+    _check_amp_state(amp_state)
+    check(lib().pso_adamw_step_amp(param.numel(), ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), float(lr),
+                                   float(betas[0]), float(betas[1]), float(eps), float(weight_decay), ptr(amp_state),
+                                   stream_ptr()), "pso_adamw_step_amp")
+
+
+def adamw8bit_step_amp(param, grad, state, lr, betas, eps, weight_decay, amp_state, out_bf16=None, zero_grad=False):
+    """adamw8bit_step (per-tensor block tables only) driven by the loss-scaler state; returns whether the gradient
+    was zeroed -- it is on a skipped step too."""
+    require_cuda(param, grad)
+    _check_amp_state(amp_state)
+    if state.desc is None:
+        raise _lib.PsoLibError("adamw8bit_step_amp needs a per-tensor block table (Adam8State(segments=...))")
+    if out_bf16 is not None:
+        assert out_bf16.dtype == ELEM and out_bf16.numel() == param.numel() and out_bf16.is_contiguous()
+    fn = "pso_adamw8bit_step_blocks_zero_grad_amp" if zero_grad else "pso_adamw8bit_step_blocks_amp"
+    check(getattr(lib(), fn)(param.numel(), state.nblk, ptr(state.desc), ptr(param), ptr(out_bf16), ptr(grad),
+                             ptr(state.qm), ptr(state.qv), ptr(state.am), ptr(state.av), ptr(state.m32),
+                             ptr(state.v32), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                             float(weight_decay), ptr(amp_state), stream_ptr()), fn)
+    return zero_grad
+
+
 def zero_(x):
     check(lib().pso_zero_f32(x.numel(), ptr(x), stream_ptr()), "pso_zero_f32")
     return x

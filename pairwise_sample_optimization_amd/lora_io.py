@@ -9,7 +9,10 @@
 * `save_state(trainer, dir)` / `load_state(trainer, dir)` -- resume (`T:886-890`, `accelerator.save_state`): the
   LoRA file plus the AdamW moments and step count (`optimizer.safetensors`).  8-bit AdamW checkpoints carry the
   per-tensor block table (round 4 on); an older checkpoint without one (uniform 2048-element blocks over the flat
-  buffer) is re-quantised into the per-tensor layout on load, with a warning.
+  buffer) is re-quantised into the per-tensor layout on load, with a warning.  A trainer with a loss scaler
+  (`amp.LossScaler` or `amp.DeviceLossScaler`, fp16 training) also writes the scaler's `state_dict()` under the
+  additive key `loss_scaler` of `pso_state.json`; a checkpoint without it loads as before and keeps the trainer's
+  scaler as constructed.
 """
 import json
 import os
@@ -83,7 +86,11 @@ def save_state(trainer, output_dir):
     save_file(opt, os.path.join(output_dir, OPT_NAME),
               metadata={"step": str(trainer.opt_step), "n_micro": str(trainer.n_micro)})
     with open(os.path.join(output_dir, "pso_state.json"), "w") as f:
-        json.dump({"opt_step": trainer.opt_step, "n_micro": trainer.n_micro, "rank": unet.lora.r}, f)
+        meta = {"opt_step": trainer.opt_step, "n_micro": trainer.n_micro, "rank": unet.lora.r}
+        scaler = getattr(trainer, "scaler", None)
+        if scaler is not None:
+            meta["loss_scaler"] = scaler.state_dict()
+        json.dump(meta, f)
 
 
 def load_state(trainer, input_dir):
@@ -120,4 +127,7 @@ def load_state(trainer, input_dir):
         trainer.exp_avg_sq.copy_(opt["exp_avg_sq"])
     with open(os.path.join(input_dir, "pso_state.json")) as f:
         meta = json.load(f)
+    scaler = getattr(trainer, "scaler", None)
+    if scaler is not None and "loss_scaler" in meta:
+        scaler.load_state_dict(meta["loss_scaler"])
     trainer.opt_step, trainer.n_micro = int(meta["opt_step"]), int(meta["n_micro"])

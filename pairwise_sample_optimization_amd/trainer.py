@@ -27,7 +27,7 @@ import os
 from . import _lib
 from . import kernels as K
 from . import pso_core
-from .amp import LossScaler, make_scaler
+from .amp import DeviceLossScaler, LossScaler, make_scaler
 from ._lib import MODE_TURBO, MODE_DMD
 from .schedulers import EulerAncestralDiscreteScheduler, LCMScheduler, dmd_distill_timesteps
 
@@ -257,12 +257,53 @@ def _work_copy(unet, master):
     return w if ok else None
 
 
+class OptStep:
+    """trainer.opt_step, the AdamW step count: a host integer, or -- with an amp.DeviceLossScaler, whose kernels
+    advance it -- the state block's applied-step word, read back (a sync) only when somebody asks."""
+
+    def __get__(self, tr, owner=None):
+        if tr is None:
+            return self
+        sc = getattr(tr, "scaler", None)
+        return sc.step if isinstance(sc, DeviceLossScaler) else tr.__dict__.get("opt_step", 0)
+
+    def __set__(self, tr, value):
+        sc = getattr(tr, "scaler", None)
+        if isinstance(sc, DeviceLossScaler):
+            sc.step = int(value)
+        else:
+            tr.__dict__["opt_step"] = int(value)
+
+
+def _amp_optimizer_step(tr, scaler, scale):
+    """lora_optimizer_step after the all-reduce with a DeviceLossScaler: unscale / norm / clip -> AdamW -> scale
+    update -> zero -> refresh, every decision (inf-skip, step count, back-off and growth) taken by the kernels on the
+    scaler's state block.  Nothing is read back; a skipped step still refreshes the (unchanged) working copies."""
+    master, grad, refresh = trainable(tr.unet)
+    st = scaler.state
+    K.amp_unscale_clip(grad, tr.max_grad_norm, st, tr.betas, grad_scale=scale)
+    cast = True
+    if getattr(tr, "adam8", None) is not None:
+        work = _work_copy(tr.unet, master)
+        zeroed = K.adamw8bit_step_amp(master, grad, tr.adam8, tr.lr, tr.betas, tr.adam_eps, tr.wd, st, out_bf16=work,
+                                      zero_grad=True)
+        cast = work is None
+    else:
+        zeroed = False
+        K.adamw_step_amp(master, grad, tr.exp_avg, tr.exp_avg_sq, tr.lr, tr.betas, tr.adam_eps, tr.wd, st)
+    K.amp_update(st, scaler.growth_factor, scaler.backoff_factor, scaler.growth_interval)
+    if not zeroed:
+        K.zero_(grad)
+    refresh(cast=cast)
+
+
 def lora_optimizer_step(tr):
     """accelerator.backward's sync step + clip_grad_norm_ + optimizer.step + zero_grad (T:857-861, DB:1953-1964) on
     the flat LoRA bucket of tr.unet: RCCL all-reduce -> global-norm clip coefficient -> fused AdamW (clip and 1/world
     folded into the gradient read) -> zero -> refresh the bf16 working copies.  tr carries exp_avg, exp_avg_sq,
     opt_step, clip_buf, lr, betas, adam_eps, wd, max_grad_norm, pg and, when the last backward of the window already
-    issued the bucketed all-reduce (tr.sync_armed), the GradBuckets to finish."""
+    issued the bucketed all-reduce (tr.sync_armed), the GradBuckets to finish.  fp16 training: tr.scaler is an
+    amp.LossScaler (the norm is read back, one sync) or an amp.DeviceLossScaler (_amp_optimizer_step: no read-back)."""
     master, grad, refresh = trainable(tr.unet)
     if getattr(tr, "sync_armed", False):
         scale = tr.buckets.finish()
@@ -270,6 +311,8 @@ def lora_optimizer_step(tr):
     else:
         scale = allreduce_grads(grad, tr.pg, getattr(tr, "allreduce_dtype", None))
     scaler = getattr(tr, "scaler", None)
+    if isinstance(scaler, DeviceLossScaler):
+        return _amp_optimizer_step(tr, scaler, scale)
     if scaler is not None:
         # fp16 loss scaling (amp.LossScaler): the backward ran on loss * S, so unscale in the gradient read.  The norm
         # of the all-reduced gradient is read back -- the one sync per optimizer step, where GradScaler.step syncs --
@@ -302,14 +345,17 @@ def lora_optimizer_step(tr):
 
 
 class PSOTrainer:
+    opt_step = OptStep()
+
     def __init__(self, unet, mode="turbo", num_steps=2, beta=50.0, clip_eps=0.1, lr=1e-5, betas=(0.9, 0.999),
                  weight_decay=1e-6, adam_eps=1e-8, max_grad_norm=1.0, gradient_accumulation_steps=1,
                  train_batch_size=1, num_reward=1, process_group=None, max_pass_images=16, ref_unet=None,
                  latent_dtype=torch.float32, allreduce_dtype=None, use_8bit_adam=False, overlap_sync=None,
                  bucket_mb=32.0, loss_scale=None):
         self.unet = unet
-        # loss_scale: None (no scaling), a float (initial scale) or an amp.LossScaler: dynamic loss scaling with
-        # inf-skip for fp16 training.  Active under the f16 library only -- bf16 has fp32's exponent range.
+        # loss_scale: None (no scaling), a float (initial scale), an amp.LossScaler or an amp.DeviceLossScaler (state
+        # on the device, no sync in the optimizer step): dynamic loss scaling with inf-skip for fp16 training.
+        # Active under the f16 library only -- bf16 has fp32's exponent range.
         self.scaler = make_scaler(loss_scale)
         if self.scaler is not None and ELEM != torch.float16:
             raise ValueError("loss_scale is for fp16 training (PSO_LIB=f16, libpso_amd_f16.so); the loaded library "
@@ -386,7 +432,7 @@ class PSOTrainer:
 
     @classmethod
     def from_config(cls, unet, config, mode="turbo", num_reward=1, process_group=None, ref_unet=None,
-                    latent_dtype=None):
+                    latent_dtype=None, loss_scale=None):
         """Build from a reference run config (`config_sdxl_{turbo,dmd}_dpo.get_config()`): sample.num_steps,
         train.{beta, eps, learning_rate, adam_*, max_grad_norm, gradient_accumulation_steps, batch_size}.
         Both trainers require `distilled_train_steps == num_steps - 1` (turbo asserts it at T:221; DMD2 asserts
@@ -395,7 +441,9 @@ class PSOTrainer:
         weight_dtype (D:329-333; drawn in prompt_embeds.dtype, DP/sdxl_dmd_with_logprob.py:91-101), so its step /
         log-prob arithmetic runs in that dtype (DP/distilled_inference_with_logprob.py:84-135) -> the replay mode of
         that dtype; pass torch.float32 to train on the fp32 step math instead.  A value that disagrees with the
-        config is honoured with a warning."""
+        config is honoured with a warning.
+        loss_scale (f16 library only): the scaler to train with instead of the default host amp.LossScaler(), e.g.
+        an amp.DeviceLossScaler."""
         tr = config.train
         if tr.distilled_train_steps != config.sample.num_steps - 1:
             raise AssertionError("train.distilled_train_steps must equal sample.num_steps - 1 "
@@ -408,14 +456,14 @@ class PSOTrainer:
             import warnings
             warnings.warn(f"PSOTrainer.from_config: latent_dtype {latent_dtype} differs from the config's "
                           f"mixed_precision={mp!r} (reference latents: {cfg_dtype})")
-        loss_scale = None
         if ELEM == torch.float16:
             # the f16 library runs the reference's own recipe: fp16 UNet arithmetic, fp32 LoRA parameters, dynamic
             # loss scaling with inf-skip.  A config that asks for another precision belongs to the bf16 library.
             if mp != "fp16":
                 raise ValueError(f"the f16 library (PSO_LIB=f16) trains mixed_precision='fp16' configs only, got "
                                  f"{mp!r}: unset PSO_LIB for the bf16 library")
-            loss_scale = LossScaler()
+            if loss_scale is None:
+                loss_scale = LossScaler()
         return cls(unet, mode=mode, num_steps=config.sample.num_steps, beta=float(tr.beta), clip_eps=float(tr.eps),
                    lr=tr.learning_rate, betas=(tr.adam_beta1, tr.adam_beta2), weight_decay=tr.adam_weight_decay,
                    adam_eps=tr.adam_epsilon, max_grad_norm=tr.max_grad_norm,
@@ -590,8 +638,12 @@ class PSOTrainer:
         loss, lp = K.pair_loss_fwd(self.mode, mb.x, mb.x_next, eps_pol, eps_ref, mb.coef, pref, self.beta,
                                    self.clip_eps, ws)
         # accelerator.backward divides by gradient_accumulation_steps (accelerate accelerator.py:2840)
-        deps = K.pair_loss_bwd(self.mode, mb.x, mb.x_next, eps_pol, mb.coef, pref, self.beta, self.clip_eps, ws,
-                               grad_scale=count / self.gas_total * self.loss_scale)
+        if isinstance(self.scaler, DeviceLossScaler):  # the scale is read on the device (no host copy of it exists)
+            deps = K.pair_loss_bwd(self.mode, mb.x, mb.x_next, eps_pol, mb.coef, pref, self.beta, self.clip_eps, ws,
+                                   grad_out=self.scaler.scale_word, grad_scale=count / self.gas_total)
+        else:
+            deps = K.pair_loss_bwd(self.mode, mb.x, mb.x_next, eps_pol, mb.coef, pref, self.beta, self.clip_eps, ws,
+                                   grad_scale=count / self.gas_total * self.loss_scale)
         if self.overlap_sync and self.auto_step and (self.n_micro + count) % self.gas_total == 0:
             rt.unit_done = self.buckets.hook(rt)  # the window's last backward: overlap the gradient all-reduce
             self.sync_armed = True
@@ -611,7 +663,7 @@ class PSOTrainer:
     @property
     def loss_scale(self):
         """The factor on the loss in backward: a power of two, constant within an accumulation window (it changes
-        only in optimizer_step); 1.0 without a scaler."""
+        only in optimizer_step); 1.0 without a scaler.  With a DeviceLossScaler this reads the device (a sync)."""
         return 1.0 if self.scaler is None else self.scaler.scale
 
     _SB_TENSORS = ("x", "x_next", "unet_in", "enc", "pooled", "tid", "t", "coef", "rewards")
@@ -620,8 +672,8 @@ class PSOTrainer:
         """train_epoch as ONE hipGraph replay (torch.cuda.CUDAGraph over the HIP runtime): the epoch's micro-steps --
         paired UNet pass, fused loss, backward into the flat LoRA grad bucket -- are captured on the first call and
         replayed afterwards, so the ~7k kernel launches of an epoch cost one graph launch instead of one host call
-        each.  The shuffled buffer is copied into the graph's static input buffers first; the optimizer step (its
-        AdamW step count is a host scalar) runs eagerly after the replay.  Requires: the epoch is exactly one
+        each.  The shuffled buffer is copied into the graph's static input buffers first; the optimizer step (with
+        its all-reduce) runs eagerly after the replay.  Requires: the epoch is exactly one
         accumulation window starting at a window boundary, and the turbo sampler draws no reward column (m = 1);
         otherwise this is train_epoch."""
         if (sb.n_micro != self.gas_total or self.n_micro % self.gas_total or not self.auto_step
@@ -631,8 +683,11 @@ class PSOTrainer:
             # full-UNet training: the optimizer step rebuilds the kernel-layout weight caches as new tensors
             # (refresh_full -> prepare), which a captured graph would keep reading at their old addresses
             return self.train_epoch(sb, generator)
-        # the loss scale is a host float baked into the captured loss backward: a change re-captures (rare)
-        key = tuple((k, tuple(getattr(sb, k).shape)) for k in self._SB_TENSORS) + (("loss_scale", self.loss_scale),)
+        key = tuple((k, tuple(getattr(sb, k).shape)) for k in self._SB_TENSORS)
+        if not isinstance(self.scaler, DeviceLossScaler):
+            # the loss scale is a host float baked into the captured loss backward: a change re-captures (rare).  A
+            # device scaler's scale is read by the captured kernels: one capture serves every scale.
+            key += (("loss_scale", self.loss_scale),)
         g = getattr(self, "_graph", None)
         if g is None or self._graph_key != key:
             self._graph = None
