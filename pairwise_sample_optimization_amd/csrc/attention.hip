@@ -1665,6 +1665,7 @@ static int cross_qsplit(int B, int H, int Sq, int Sk) {
 
 
 static bool a16(const void* p, long ld) { return (((uintptr_t)p) & 15) == 0 && (ld % 8) == 0; }
+static bool a8(const void* p, long ld) { return (((uintptr_t)p) & 7) == 0 && (ld % 4) == 0; }
 
 extern "C" {
 
@@ -1745,6 +1746,13 @@ int pso_attention_bwd(int B, int H, int Sq, int Sk, const void* q, long ldq, lon
   PSO_ARG_CHECK(ws_bytes >= pso_attention_bwd_ws_bytes(B, H, Sq, Sk), "pso_attention_bwd: workspace too small");
   PSO_ARG_CHECK(a16(q, ldq) && a16(k, ldk) && a16(v, ldv) && a16(o, ldo) && a16(dO, lddo),
                 "pso_attention_bwd: operands need 16-B aligned rows");
+  // dQ / dK / dV leave the kernels (reduce_splits_kernel included) as 8-byte uint2 stores
+  PSO_ARG_CHECK(a8(dq, lddq) && a8(dk, lddk) && a8(dv, lddv),
+                "pso_attention_bwd: dq/dk/dv need 8-B aligned rows (pointer % 8 == 0, row stride % 4 == 0)");
+  // reduce_splits_kernel walks dk / dv as B * Sk rows of one stride: it has no batch stride of its own
+  PSO_ARG_CHECK(cross_qsplit(B, H, Sq, Sk) == 1 || (sdk_b == (long)Sk * lddk && sdv_b == (long)Sk * lddv),
+                "pso_attention_bwd: the query-split path needs dk/dv batch strides of Sk rows "
+                "(sdk_b == Sk*lddk, sdv_b == Sk*lddv)");
   hipStream_t st = (hipStream_t)stream;
   AttnArgs a{};
   a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v;

@@ -51,6 +51,56 @@ def test_no_cpu_fallback():
         kernels.gemm(a, a)
 
 
+_ATTN_BWD_ARG_PROBE = """
+import torch
+from pairwise_sample_optimization_amd import _lib
+assert not torch.cuda.is_available()
+l = _lib.lib()
+B, H, Sq, Sk, C = 2, 5, 300, 77, 320   # the short-key backward with 5 query splits
+assert l.pso_attention_bwd_ws_bytes(B, H, Sq, Sk) > 2 * 256 * -(-(B * H * Sq * 4) // 256)
+IN = 0x10000                            # fake, never dereferenced: every case below fails a check before any launch
+ok = dict(dq=0x20000, lddq=C, sdq_b=Sq * C, dk=0x30000, lddk=C, sdk_b=Sk * C, dv=0x40000, lddv=C, sdv_b=Sk * C)
+cases = [("dq+4B", dict(dq=0x20004)), ("dk+4B", dict(dk=0x30004)), ("dv+4B", dict(dv=0x40004)),
+         ("lddq%4", dict(lddq=C + 2, sdq_b=Sq * (C + 2))), ("lddk%4", dict(lddk=C + 2, sdk_b=Sk * (C + 2))),
+         ("lddv%4", dict(lddv=C + 2, sdv_b=Sk * (C + 2))),
+         ("sdk_b", dict(sdk_b=(Sk + 3) * C)), ("sdv_b", dict(sdv_b=(Sk + 3) * C))]
+for name, bad in cases:
+    a = dict(ok, **bad)
+    rc = l.pso_attention_bwd(B, H, Sq, Sk, IN, C, Sq * C, IN, C, Sk * C, IN, C, Sk * C, IN, C, Sq * C, IN, IN, C,
+                             Sq * C, 0.125, a["dq"], a["lddq"], a["sdq_b"], a["dk"], a["lddk"], a["sdk_b"], a["dv"],
+                             a["lddv"], a["sdv_b"], IN, 1 << 40, None)
+    print("case", name, rc, l.pso_last_error().decode())
+"""
+
+
+def test_attention_bwd_checks_output_alignment_and_split_batch_stride():
+    """pso_attention_bwd stores dQ / dK / dV 8 bytes at a time, and its query-split reduction walks dK / dV as B * Sk
+    rows of one stride: both are argument checks of the C entry point, in all three library builds.  Called with small
+    fake addresses that break each rule in turn; every call must come back PSO_ERR_ARG with a message that names the
+    rule (on a machine without a device a launch would return non-zero too: only the message tells them apart).
+    Host-only on purpose: with a GPU present a regression would launch on the fake pointers, so the test skips itself
+    there."""
+    import sys
+    import pytest
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("argument checks are exercised where no launch can follow a regression (no GPU)")
+    for pso_lib in (None, "knobs", "f16"):
+        env = {k: v for k, v in os.environ.items() if k not in ("PSO_LIB", "PSO_LIB_PATH")}
+        if pso_lib:
+            env["PSO_LIB"] = pso_lib
+        r = subprocess.run([sys.executable, "-c", _ATTN_BWD_ARG_PROBE], env=env, cwd=ROOT, capture_output=True,
+                           text=True, timeout=300)
+        assert r.returncode == 0, (pso_lib, r.stdout[-2000:] + r.stderr[-2000:])
+        got = {m.group(1): (int(m.group(2)), m.group(3))
+               for m in re.finditer(r"^case (\S+) (-?\d+) (.*)$", r.stdout, flags=re.M)}
+        assert len(got) == 8, (pso_lib, r.stdout)
+        for name, (rc, msg) in got.items():
+            assert rc == 1, (pso_lib, name, rc, msg)  # PSO_ERR_ARG
+            want = "dk/dv batch strides of Sk rows" if name.startswith("sd") else "dq/dk/dv need 8-B aligned rows"
+            assert msg.startswith("pso_attention_bwd: ") and want in msg, (pso_lib, name, msg)
+
+
 def test_product_library_has_no_benchmark_knobs():
     """the benchmark knobs (include/pso_amd_knobs.h) and the measured-not-kept kernel forms live in the
     tools build only.  The product library exports none of the knob setters, reads no environment variable, and holds

@@ -273,6 +273,14 @@ def test_attention_fwd_bwd(cuda, B, H, Sq, Sk):
     assert (lse - torch.logsumexp(f(q) @ f(k).transpose(-1, -2) * 0.125, dim=-1)).abs().max().item() < 2e-3
 
 
+@pytest.mark.parametrize("B,H,Sq,Sk", [(2, 5, 300, 77), (2, 2, 200, 191)])
+def test_attention_strided_in_guarded_out(cuda, B, H, Sq, Sk):
+    """The two ragged, query-split cases of tests/test_gpu_attention_layout.py on the fp16 library: strided inputs,
+    outputs in guard-banded column slices, per-row error over all heads within 3 x the fp16 rounding model's."""
+    import parity_util as P
+    P.run_attention_case(cuda, B, H, Sq, Sk, True)
+
+
 @pytest.mark.parametrize("silu", [False, True])
 def test_group_norm_fwd_bwd(cuda, silu):
     from pairwise_sample_optimization_amd import kernels as Kk

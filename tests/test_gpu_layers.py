@@ -6,6 +6,8 @@ import torch
 
 import torch.nn.functional as F
 
+import parity_util as P
+
 pytestmark = pytest.mark.gpu
 
 
@@ -109,15 +111,23 @@ def test_attention_bwd_short_kv_fused(cuda, B, H, Sq, Sk):
     b = K.attention_bwd(q, k, v, o, lse, do, H)
     for x, y in zip(a, b):
         assert torch.equal(x, y)
-    hs = min(H, 4)  # fp32 reference on the first heads
-    f = lambda t: t.float().view(B, -1, H, 64)[:, :, :hs].transpose(1, 2).detach().requires_grad_(True)
+    # fp32 reference on ALL heads (a head offset past the fourth is as easy to get wrong as one before it)
+    f = lambda t: t.float().view(B, -1, H, 64).transpose(1, 2).detach().requires_grad_(True)
     qf, kf, vf = f(q), f(k), f(v)
     ref = torch.softmax(qf @ kf.transpose(-1, -2) / 8.0, -1) @ vf
-    ref.backward(do.float().view(B, -1, H, 64)[:, :, :hs].transpose(1, 2))
+    ref.backward(do.float().view(B, -1, H, 64).transpose(1, 2))
     for name, mine, r in zip(("dq", "dk", "dv"), a, (qf.grad, kf.grad, vf.grad)):
-        m = mine.float().view(B, -1, H, 64)[:, :, :hs].transpose(1, 2)
+        m = mine.float().view(B, -1, H, 64).transpose(1, 2)
         assert ((m - r).norm() / r.norm()).item() < 2e-2, name
         assert torch.isfinite(mine).all(), name
+    del ref, qf, kf, vf
+    # and per (batch, row, head) against fp64, within 3 x the rounding model's own worst row (tests/parity_util.py)
+    ref64 = P.attention_fp64(q, k, v, do, H, 0.125)
+    worst_model = P.attention_row_bounds(P.attention_model(q, k, v, do, H, 0.125), ref64)
+    for name, mine, r in zip(("o", "dq", "dk", "dv"), [o] + a, (ref64[0],) + ref64[2:]):
+        e = P.rowwise_rel(mine, r, 64)
+        print(f"\n[rows short-kv {(B, H, Sq, Sk)}] {name} kernel {e} model {worst_model[name]}", flush=True)
+        assert e < P.ROW_BOUND_FACTOR * worst_model[name], (name, e, worst_model[name])
 
 
 @pytest.mark.parametrize("B,H,Sq,Sk", [(2, 5, 300, 77), (1, 2, 100, 100), (1, 4, 130, 1000)])
@@ -339,3 +349,174 @@ def test_casts_vectorised_and_ragged(cuda, n):
         y = torch.empty(n + 4, device=cuda)
         K.cast_bf16_f32(b, out=y[off:off + n])
         assert torch.equal(y[off:off + n], b.float())
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# element-wise wrappers that no other test calls by name: a few lines each against plain torch, at ragged sizes.  The
+# vectorised ones (8 elements per thread) take multiples of 8 only: the other sizes must be refused as an argument
+# error -- never run as something else -- and must leave the output untouched.
+# ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("N", [1, 77, 1000, 4100, 8, 80, 2048, 4104])
+def test_softmax_rows_strided_in_place(cuda, N):
+    """pso_softmax_rows in place on a row-strided view inside a guard-banded buffer (the VAE's mid attention calls it
+    on score rows), rows with one very large logit and all-equal rows included: per-row error against fp64 within 3 x
+    that of an fp32 softmax rounded to the element type; the gaps and guard rows keep their bits.  N must be a multiple
+    of 8 (16-byte row accesses): 1, 77 and 4100 are refused."""
+    from pairwise_sample_optimization_amd import kernels as K
+    from pairwise_sample_optimization_amd._lib import PsoLibError
+    M = 37
+    g = torch.Generator().manual_seed(N)
+    x0 = (3 * torch.randn(M, N, generator=g))
+    x0[5, N // 2] = 80.0          # one logit far above the rest: every other weight underflows towards 0
+    x0[20, N - 1] = 200.0
+    x0[21] = -150.0               # all equal, far from 0: exp(a - max) = 1 everywhere
+    x0[22, 0] = -300.0
+    x0 = x0.bfloat16().to(cuda)
+    (x,), check = P.guarded(M, [N], device=cuda)
+    x.copy_(x0)
+    if N % 8:
+        with pytest.raises(PsoLibError, match="multiples of 8"):
+            K.softmax_rows(x)
+        torch.cuda.synchronize()
+        check()
+        assert torch.equal(x, x0)
+        return
+    assert K.softmax_rows(x).data_ptr() == x.data_ptr()
+    torch.cuda.synchronize()
+    check(f"softmax_rows N={N}")
+    ref = torch.softmax(x0.double(), -1)
+    model = torch.softmax(x0.float(), -1).bfloat16()
+    e, em = P.rowwise_rel(x, ref, N), P.rowwise_rel(model, ref, N)
+    print(f"\n[rows softmax N={N}] kernel {e} model {em}", flush=True)
+    assert torch.isfinite(x).all() and e < P.ROW_BOUND_FACTOR * em, (e, em)
+    assert (x.double().sum(-1) - 1).abs().max().item() < 2.0 ** -8 * 2  # rows still sum to 1 to bf16 rounding
+
+
+@pytest.mark.parametrize("C1,C2", [(8, 320), (320, 8), (320, 320), (8, 8), (4, 8), (324, 320), (8, 324), (320, 4)])
+def test_concat_split_channels(cuda, C1, C2):
+    """concat_channels / split_channels (the UNet's skip connections and their gradients) on an odd pixel count: pure
+    data movement is bit-exact; split's add2 is one fp32 add, rounded once.  Channel counts must be multiples of 8
+    (4 and 324 are refused)."""
+    from pairwise_sample_optimization_amd import kernels as K
+    from pairwise_sample_optimization_amd._lib import PsoLibError
+    g = torch.Generator().manual_seed(C1 * 7 + C2)
+    x1 = torch.randn(3, 7, 5, C1, generator=g).bfloat16().to(cuda)
+    x2 = torch.randn(3, 7, 5, C2, generator=g).bfloat16().to(cuda)
+    add2 = torch.randn(3, 7, 5, C2, generator=g).bfloat16().to(cuda)
+    cat = torch.cat([x1, x2], -1)
+    if C1 % 8 or C2 % 8:
+        with pytest.raises(PsoLibError, match="pso_concat_channels"):
+            K.concat_channels(x1, x2)
+        with pytest.raises(PsoLibError, match="pso_split_channels"):
+            K.split_channels(cat, C1)
+        return
+    out = K.concat_channels(x1, x2)
+    assert out.shape == cat.shape and torch.equal(out, cat)
+    y1, y2 = K.split_channels(cat, C1)
+    assert torch.equal(y1, x1) and torch.equal(y2, x2)
+    y1, y2 = K.split_channels(cat, C1, add2=add2)
+    assert torch.equal(y1, x1) and torch.equal(y2, (x2.float() + add2.float()).bfloat16())
+
+
+@pytest.mark.parametrize("n", [8, 1003, 4096 * 37 + 5, 1000, 4096 * 37 + 8])
+def test_axpby_plain_z_and_aliased(cuda, n):
+    """axpby: plain (y = a x), with z (y = a x + b z), and aliased out = x as unet.py scales the LoRA B matrices in
+    place.  fp32 arithmetic and one rounding: |y - ref| <= 2^-8 |ref| + 2^-22 (|a x| + |b z|) element-wise against
+    fp64 (2^-8: bf16's unit roundoff; the second term covers the fp32 product, sum and a fused multiply-add).  n must be
+    a multiple of 8 (1003 and 4096 * 37 + 5 are refused)."""
+    from pairwise_sample_optimization_amd import kernels as K
+    from pairwise_sample_optimization_amd._lib import PsoLibError
+    g = torch.Generator().manual_seed(n)
+    x = torch.randn(n, generator=g).bfloat16().to(cuda)
+    z = torch.randn(n, generator=g).bfloat16().to(cuda)
+    if n % 8:
+        with pytest.raises(PsoLibError, match="pso_axpby"):
+            K.axpby(0.5, x)
+        return
+    a, b = 0.37, -1.25
+
+    def ok(y, ref, mag):
+        return bool(((y.double() - ref).abs() <= 2.0 ** -8 * ref.abs() + 2.0 ** -22 * mag).all())
+
+    af, bf_ = float(torch.tensor(a).float()), float(torch.tensor(b).float())  # the scalars travel as C floats
+    assert ok(K.axpby(a, x), af * x.double(), (af * x.double()).abs())
+    ref = af * x.double() + bf_ * z.double()
+    mag = (af * x.double()).abs() + (bf_ * z.double()).abs()
+    assert ok(K.axpby(a, x, b, z), ref, mag)
+    assert torch.equal(K.add(x, z), (x.float() + z.float()).bfloat16())  # a = b = 1: one exact fp32 sum, one rounding
+    (buf,), check = P.guarded(1, [n], device=cuda)
+    xa = buf[0]
+    xa.copy_(x)
+    assert K.axpby(a, xa, b, z, out=xa).data_ptr() == xa.data_ptr()
+    torch.cuda.synchronize()
+    check(f"axpby n={n}")
+    assert ok(xa, ref, mag)
+
+
+@pytest.mark.parametrize("mode", ["gelu", "quick_gelu"])
+def test_activation_modes_of_clip(cuda, mode):
+    """activation_ in the two modes clip.py passes (erf GELU, quick GELU), in place on a ragged element count with
+    large arguments of both signs: |y - ref| <= 2^-8 |ref| + 2^-20 |x| against fp64 (one bf16 rounding; the absolute
+    term covers fp32's 1 + erf cancellation and the fast exponential in the negative tail)."""
+    from pairwise_sample_optimization_amd import kernels as K
+    from pairwise_sample_optimization_amd.clip import _ACTS
+    assert set(_ACTS) == {"gelu", "quick_gelu"}
+    g = torch.Generator().manual_seed(5)
+    x0 = (2 * torch.randn(37, 1003, generator=g))
+    x0[0, :8] = torch.tensor([0.0, -0.0, 8.0, -8.0, 30.0, -30.0, 1e-3, -1e-3])
+    x0 = x0.bfloat16().to(cuda)
+    x = x0.clone()
+    assert K.activation_(x, _ACTS[mode]).data_ptr() == x.data_ptr()
+    xd = x0.double()
+    ref = 0.5 * xd * torch.erfc(-xd / 2 ** 0.5) if mode == "gelu" else xd * torch.sigmoid(1.702 * xd)
+    err = (x.double() - ref).abs()
+    assert torch.isfinite(x).all()
+    assert bool((err <= 2.0 ** -8 * ref.abs() + 2.0 ** -20 * xd.abs()).all()), err.max().item()
+
+
+def test_embed_tokens_and_vision(cuda):
+    """embed_tokens = tok[ids] + pos[:S]; embed_vision = [class + pos[0]; patch[b][p] + pos[1 + p]] per image: one
+    fp32 add, one rounding -- bit-exact against torch; repeated and out-of-order ids, C no multiple of the block."""
+    from pairwise_sample_optimization_amd import kernels as K
+    g = torch.Generator().manual_seed(9)
+    B, S, C, V = 3, 7, 100, 50
+    tok = torch.randn(V, C, generator=g).bfloat16().to(cuda)
+    pos = torch.randn(S + 2, C, generator=g).bfloat16().to(cuda)
+    ids = torch.randint(0, V, (B, S), generator=g).to(cuda)
+    ids[0, 0], ids[0, 1], ids[2, 6] = V - 1, V - 1, 0
+    out = K.embed_tokens(ids, tok, pos)
+    assert out.shape == (B * S, C)
+    assert torch.equal(out.view(B, S, C), (tok[ids].float() + pos[:S].float()).bfloat16())
+    Pn, C = 5, 72
+    patch = torch.randn(B * Pn, C, generator=g).bfloat16().to(cuda)
+    cls = torch.randn(C, generator=g).bfloat16().to(cuda)
+    pos = torch.randn(Pn + 1, C, generator=g).bfloat16().to(cuda)
+    want = torch.empty(B, Pn + 1, C, device=cuda)
+    for b in range(B):
+        want[b, 0] = cls.float() + pos[0].float()
+        for p in range(Pn):
+            want[b, 1 + p] = patch[b * Pn + p].float() + pos[1 + p].float()
+    out = K.embed_vision(patch, cls, pos, B, Pn)
+    assert out.shape == (B * (Pn + 1), C) and torch.equal(out.view(B, Pn + 1, C), want.bfloat16())
+
+
+@pytest.mark.parametrize("n,C", [(9, 100), (4, 768), (1, 3)])
+def test_cosine_rows_strided(cuda, n, C):
+    """cosine_rows on row-strided fp32 views (the PickScore head): <a, b> / (|a| |b|) with fp64 sums.  There is no
+    epsilon in the denominator: a zero row gives 0 / 0 = NaN (torch.cosine_similarity would give 0), and only that row."""
+    from pairwise_sample_optimization_amd import kernels as K
+    g = torch.Generator().manual_seed(n + C)
+    a = torch.randn(n, C + 5, generator=g).to(cuda)[:, 3:3 + C]
+    b = torch.randn(n, 2 * C, generator=g).to(cuda)[:, C:]
+    zero = n - 1 if n > 1 else None
+    if zero is not None:
+        a[zero] = 0
+    out = K.cosine_rows(a, b)
+    ad, bd = a.double(), b.double()
+    ref = (ad * bd).sum(-1) / (ad.norm(dim=-1) * bd.norm(dim=-1))
+    keep = torch.ones(n, dtype=torch.bool, device=cuda)
+    if zero is not None:
+        keep[zero] = False
+        assert torch.isnan(out[zero])
+    assert torch.isfinite(out[keep]).all() and (out[keep].double() - ref[keep]).abs().max().item() < 1e-6
+    assert out[keep].abs().max().item() <= 1 + 1e-6
