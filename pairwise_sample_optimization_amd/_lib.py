@@ -162,9 +162,29 @@ SIGNATURES = {
 }
 
 
+class PsoGemmPlanQuery(ctypes.Structure):
+    """include/pso_amd_knobs.h PsoGemmPlanQuery: a GEMM problem by value (alignments in bytes, 0 = operand absent)."""
+    _fields_ = ([(n, ci) for n in ("variant", "group", "tn_split", "have_ws", "M", "N", "K1", "K2")] +
+                [(n, cl) for n in ("lda1", "ldb1", "lda2", "ldb2")] +
+                [(n, ci) for n in ("tail_group_n", "tail_rows", "batch", "out_dtype", "accumulate", "bias_align",
+                                   "rowbias_align", "resid_align", "out_align")] +
+                [(n, cl) for n in ("ld_rowbias", "ldr", "ldo")] + [("rows_per_group", ci), ("alpha", cf)] +
+                [(n, ci) for n in ("conv_mode", "B", "C1", "C2", "H", "W", "Ho", "Wo", "ks", "stride", "pad",
+                                   "tn_group")])
+
+
+class PsoGemmPlanInfo(ctypes.Structure):
+    """include/pso_amd_knobs.h PsoGemmPlanInfo: what csrc/gemm_plan.h decides."""
+    _fields_ = [(n, ci) for n in ("form", "bm", "bn", "wm", "wn", "stages", "pipe", "epi", "conv_mode", "atomic_ks",
+                                  "ws_ks", "stage_epi", "vec_ok", "group_m")]
+
+
+PLAN_GEMM, PLAN_CONV, PLAN_BATCHED, PLAN_GEGLU, PLAN_GEGLU_BWD, PLAN_TN, PLAN_TN_GEGLU = range(7)  # enum PsoGemmPlanKind
+
 # include/pso_amd_knobs.h: bound only when the TOOLS build is loaded (PSO_LIB=knobs)
 KNOB_SIGNATURES = {
     "pso_gemm_set_variant": (None, [ci]),
+    "pso_gemm_plan_query": (ci, [ci, ctypes.POINTER(PsoGemmPlanQuery), ctypes.POINTER(PsoGemmPlanInfo)]),
     "pso_gemm8p_skip_epilogue": (None, [ci]),
     "pso_gemm_tn_set_split": (None, [ci]),
     "pso_attention_set_variant": (None, [ci]),

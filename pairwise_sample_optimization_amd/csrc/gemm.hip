@@ -17,52 +17,16 @@
 // an XOR swizzle (chunk ^ (row & 7)) that makes both the ds_write_b128 and the ds_read_b128 fragment reads
 // conflict-free on 128-B rows.  The MFMA is issued with the B (weight) fragment first so that every lane ends up
 // holding 4 consecutive output columns of one row -> 8-B / 16-B vector epilogue stores.
-#include "common.h"
+//
+// Which kernel runs is decided in gemm_plan.h (facts -> plan, plain host C++); this file fills the facts, launches what
+// the plan says, and holds the device code of the 2-phase tiles and the TN kernels.
+#include "gemm_args.h"
+#include "gemm_plan.h"
 
 #include <cstdlib>
 
 #define GEMM_THREADS 256
 #define BK 64
-
-struct ConvGeom {
-  int mode;      // 0 = dense A, else PSO_CONV_* gather
-  const bf16_t* src2;  // second channel source (concat) or null
-  int C1, C2;    // channels of src1 (A1) and src2
-  int H, W;      // input spatial size (source grid)
-  int Ho, Wo;    // output spatial size
-  int ks, stride, pad;
-};
-
-struct GemmArgs {
-  const bf16_t* a1; long lda1; int K1;
-  const bf16_t* b1; long ldb1;
-  const bf16_t* a2; long lda2; int K2;
-  const bf16_t* b2; long ldb2;
-  int tail_group_n;  // >0: the A2 tail of output columns [j*G, (j+1)*G) starts at A2 column j*K2
-  int tail_m;        // rows >= tail_m get no A2 tail (policy + reference images in one pass: LoRA on the first rows)
-  int M, N;
-  ConvGeom conv;
-  float alpha;
-  const bf16_t* bias;
-  const bf16_t* rowbias; long ld_rowbias; int rows_per_group;
-  const bf16_t* resid; long ldr;
-  void* out; long ldo; int out_dtype; int accumulate;
-  int vec_ok;  // 4-wide epilogue vectors are aligned
-  int stage_epi;  // bf16 EPI_NONE epilogue staged through LDS: 16-B coalesced residual loads / output stores
-  int group_m;  // tile rows per raster group (>= 1)
-  // GEGLU epilogues (diffusers GEGLU: [h | gate] = x W^T + b, out = h * gelu(gate)), weight rows interleaved per 64
-  // columns as [h 32 | gate 32]:  EPI_GEGLU writes out = h*gelu(gate) (N/2 columns) and, if out2, the interleaved
-  // pre-activation;  EPI_GEGLU_BWD takes the GEMM result as dout (N columns), aux = interleaved pre-activation, and
-  // writes the interleaved input gradient [dout*gelu(g) | dout*h*gelu'(g)] to out (2N columns).
-  void* out2; long ldo2;
-  const bf16_t* aux; long ldaux;
-  // batched form (gridDim.z = batch, dense A only): operand z starts batch strides further on (elements)
-  long bat_a, bat_b, bat_o;
-  int batch;
-  // deterministic split-K (gridDim.y > 1 with ws): every split STORES its raw partial acc into ws[split][M][N]
-  // (fp32, row pitch N); gemm_splitk_reduce_kernel adds the splits in order and applies the epilogue
-  float* ws;
-};
 
 #define EPI_NONE 0
 #define EPI_GEGLU 1
@@ -804,24 +768,6 @@ int pso_gemm_skinny_nt(int M, int N, int K, const void* A, long lda, const void*
 int pso_gemm_tn_rank(int M, int C, const void* X, long ldx, const void* U, long ldu, int R, int group_c, float alpha,
                      float* out, long ldo, int out_jc, hipStream_t st);
 
-// 8-phase 256x256 kernel (gemm8p.hip): epi 0 dense (+ LoRA K-tail, bias, alpha, residual), 1 GEGLU, 2 GEGLU backward
-int pso_gemm8p_run(int epi, int M, int N, int K, const void* a, long lda, const void* w, long ldw, const void* a2,
-                   long lda2, int K2, const void* w2, long ldw2, int tail_m, int tail_group_n, float alpha,
-                   const void* bias, const void* resid, long ldr, void* out, long ldo, void* out2, long ldo2,
-                   int pre_rows, const void* aux, long ldaux, int group_m, hipStream_t st);
-int pso_gemm8p160_run(int M, int N, int K, const void* a, long lda, const void* w, long ldw, const void* a2, long lda2,
-                      int K2, const void* w2, long ldw2, int tail_m, int tail_group_n, float alpha, const void* bias,
-                      const void* resid, long ldr, void* out, long ldo, int group_m, hipStream_t st);
-int pso_gemm8p320_run(int M, int N, int K, const void* a, long lda, const void* w, long ldw, const void* a2, long lda2,
-                      int K2, const void* w2, long ldw2, int tail_m, int tail_group_n, float alpha, const void* bias,
-                      const void* resid, long ldr, void* out, long ldo, int group_m, hipStream_t st);
-int pso_gemm8p320_conv_run(int B, int H, int W, int C, const void* x, const void* w, int Cout, float alpha,
-                           const void* bias, const void* rowbias, long ld_rowbias, const void* resid, long ldr,
-                           void* out, long ldo, int group_m, hipStream_t st);
-int pso_gemm8p320_geglu_bwd_run(int M, int N, int K, const void* a, long lda, const void* w, long ldw, const void* aux,
-                                long ldaux, void* out, long ldo, int group_m, hipStream_t st);
-int pso_gemm8p320_geglu_run(int M, int N, int K, const void* a, long lda, const void* w, long ldw, const void* bias,
-                            void* out, long ldo, void* out2, long ldo2, int pre_rows, int group_m, hipStream_t st);
 static bool fits30(long rows, long ld) { return rows * ld < (1L << 30); }
 int pso_conv3x3_smallc_run(int B, int H, int W, int Cin, int Cout, const void* x, const void* w, const void* bias,
                            void* out, hipStream_t st);  // conv_small.hip
@@ -864,267 +810,121 @@ __global__ void gemm_splitk_reduce_kernel(GemmArgs g, int ks) {
   }
 }
 
-// Split-K plan of a dense GEMM whose output tiles leave CUs idle while its reduction is long (the bs = 1 / GPU
-// backward at M = 2048: 2048 x 1280 x 10240 makes 128 tiles of 128 x 160 -- half a 256-CU round at one workgroup
-// each; and one-round shapes with K >= 4096): ks K-splits of >= 16 K-tiles each, towards 512 workgroups (two per
-// CU), reduced in split order through a
-// caller-owned fp32 workspace (deterministic).  The partials cost 8 M N bytes per split against 2 M N K / ks flop,
-// so only K >= 2048 qualifies.  Returns ks (0: no split) and the tile.
-struct SplitPlan { int ks, bm, bn; };
-// Benchmark knobs (A/B variants, forced tiles, raster groups): only the tools build (-DPSO_BENCH_KNOBS ->
-// libpso_amd_knobs.so, include/pso_amd_knobs.h) has them as mutable state; the product library's are compile-time
-// zeros, so every knob branch folds away and the measured-not-kept forms are not compiled into it.
+// Benchmark knobs (gemm_plan.h GemmKnobs): mutable state in the tools build only
 #ifdef PSO_BENCH_KNOBS
-static int g_gemm_variant = 0;
+static GemmKnobs g_gemm_knobs = [] {
+  GemmKnobs k;
+  const char* e = getenv("PSO_TN128");  // benchmark knob: 0 keeps the 64 x 64 TN kernel instead of the atomic 128 x 128
+  k.tn128_off = e && atoi(e) == 0;
+  return k;
+}();
 #else
-static constexpr int g_gemm_variant = 0;
+static constexpr GemmKnobs g_gemm_knobs{};
 #endif
-static SplitPlan gemm_split_plan(int M, int N, int K1, int K2, bool has_tail, bool dense) {
-  SplitPlan p{0, 0, 0};
-  if (!dense || M <= 0 || N <= 0 || (N % 4) != 0) return p;
-  const int bm = 128, bn = (N % 160) == 0 ? 160 : 128;
-  const long tiles = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-  const int nt_all = (K1 + 63) / 64 + (has_tail ? (K2 + 63) / 64 : 0);
-  // variant 51: splits of >= 8 K-tiles (the short-K M = 2048 products: 2048 x 1280 x 1280 + LoRA in two)
-  const int min_kt = g_gemm_variant == 51 ? 8 : 16;
-  // one full round of tiles (<= 256: the 4096-row products and 3x3 convs of the bs = 1 / GPU pass, K >= 4096) splits
-  // in two as well: bs = 1 step 81.56 -> 80.25 ms, C3 237.2 -> 236.5, C2 untouched (tools/bs1_variant_ab.py, one box;
-  // K >= 2560 measured the same, up to 384 tiles cost C3 1.5 %).  Variant 55 keeps the half-round rule.
-  const bool round2 = g_gemm_variant != 55 && tiles <= 256 && nt_all >= 64;
-  if ((tiles > 128 && !round2) || nt_all < 2 * min_kt) return p;
-  int ks = (int)((512 + tiles - 1) / tiles);
-  if (ks > nt_all / min_kt) ks = nt_all / min_kt;
-  if (ks < 2) return p;
-  p.ks = ks; p.bm = bm; p.bn = bn;
-  return p;
+int pso_gemm_group_knob() { return g_gemm_knobs.group; }  // gemm8p.hip: a forced group is used as given
+
+// The facts gemm_plan.h decides on.  This is the only place that looks at the pointers of a GemmArgs.
+static GemmFacts gemm_facts(const GemmArgs& g, size_t ws_bytes, bool small_conv_entry) {
+  const ConvGeom& cv = g.conv;
+  const long hw = (long)cv.Ho * cv.Wo;
+  GemmFacts f{};
+  f.M = g.M; f.N = g.N; f.K1 = g.K1; f.K2 = g.a2 ? g.K2 : 0; f.has_tail = g.a2 != nullptr;
+  f.tail_group_n = g.tail_group_n; f.tail_m = g.tail_m; f.batch = g.batch;
+  f.out_dtype = g.out_dtype; f.accumulate = g.accumulate;
+  f.has_bias = g.bias != nullptr; f.has_rowbias = g.rowbias != nullptr; f.has_resid = g.resid != nullptr;
+  f.conv_mode = cv.mode; f.B = hw > 0 ? (int)(g.M / hw) : 0; f.C1 = cv.C1; f.C2 = cv.C2; f.H = cv.H; f.W = cv.W;
+  f.Ho = cv.Ho; f.Wo = cv.Wo; f.ks = cv.ks; f.stride = cv.stride; f.pad = cv.pad;
+  f.ab16 = al16(g.a1) && al16(g.b1);
+  f.ld_ab8 = (g.lda1 % 8) == 0 && (g.ldb1 % 8) == 0;
+  f.ld_ab_eq = g.lda1 == g.ldb1;
+  f.out16 = al16(g.out); f.out_vec = g.out_dtype == PSO_F32 ? al16(g.out) : al8(g.out);
+  f.ldo8 = (g.ldo % 8) == 0; f.ldo4 = (g.ldo % 4) == 0;
+  f.resid16 = !g.resid || (al16(g.resid) && (g.ldr % 8) == 0);
+  f.resid8 = !g.resid || (al8(g.resid) && (g.ldr % 4) == 0);
+  f.bias8 = !g.bias || al8(g.bias);
+  f.rowbias8 = !g.rowbias || al8(g.rowbias);
+  f.ld_rowbias4 = !g.rowbias || (g.ld_rowbias % 4) == 0;
+  f.rowgroup_hw = g.rows_per_group == hw;
+  f.fits_a = fits30(g.M, g.lda1); f.fits_b = fits30(g.N, g.ldb1);
+  f.fits_tail = fits30(g.tail_m, g.lda2) && fits30(g.N, g.ldb2);
+  f.fits_conv = fits30((long)g.M + 2L * (cv.W + 1), cv.C1);
+  f.have_ws = g.ws && al16(g.ws); f.ws_bytes = ws_bytes;
+  f.small_conv_entry = small_conv_entry;
+  return f;
 }
 
+// The 2-phase tile of a plan.  The product library instantiates the tiles the automatic rules choose; the forced ones
+// (A/B and tests) exist in the tools build only.  A tile that is not compiled is an error, never another tile.
+#define PSO_TILE(BM, BN, WM, WN, ST, PIPE, EPI) \
+  if (p.epi == EPI && p.tile_is(BM, BN, WM, WN, ST, PIPE)) return launch<BM, BN, WM, WN, ST, PIPE, EPI>(g, st, ks)
+static int launch_tile(const GemmPlan& p, const GemmArgs& g, hipStream_t st, int ks) {
+  PSO_TILE(64, 64, 2, 2, 2, false, EPI_NONE);
+  PSO_TILE(64, 128, 2, 2, 2, false, EPI_NONE);
+  PSO_TILE(128, 64, 2, 2, 2, false, EPI_NONE);
+  PSO_TILE(64, 160, 2, 2, 2, false, EPI_NONE);
+  PSO_TILE(128, 128, 2, 4, 2, false, EPI_NONE);
+  PSO_TILE(128, 160, 2, 2, 2, false, EPI_NONE);
+  PSO_TILE(256, 256, 2, 4, 2, false, EPI_NONE);
+  PSO_TILE(256, 256, 2, 4, 2, false, EPI_GEGLU);
+  PSO_TILE(128, 160, 2, 2, 2, false, EPI_GEGLU_BWD);
+  PSO_TILE(64, 64, 2, 2, 2, false, EPI_GEGLU_BWD);
 #ifdef PSO_BENCH_KNOBS
-static int g_tn_split = 0;  // 0 = auto (benchmark knob)  // 0 auto, 1 force 256x128x3, 2 force 128x128x3, 3 force 128x128x2 (benchmarks)
-static int g_gemm_group = 0;  // benchmark knob: raster group rows (0 = automatic)
-#else
-static constexpr int g_tn_split = 0;
-static constexpr int g_gemm_group = 0;
+#define PSO_FORCED(V, OK, BM, BN, WM, WN, ST, PIPE) PSO_TILE(BM, BN, WM, WN, ST, PIPE, EPI_NONE);
+  PSO_FORCED_TILES(PSO_FORCED)
+#undef PSO_FORCED
+  PSO_TILE(128, 128, 2, 2, 2, false, EPI_GEGLU);
+  PSO_TILE(128, 256, 2, 4, 2, false, EPI_GEGLU);
+  PSO_TILE(256, 128, 4, 2, 2, false, EPI_GEGLU);
+  PSO_TILE(128, 128, 2, 2, 3, false, EPI_GEGLU);
 #endif
-int pso_gemm_group_knob() { return g_gemm_group; }  // gemm8p.hip: a forced group is used as given
-// raster group rows: C2-step sweep (tools/_var_ab.sh, same box) 2 / 3 / 4 / 5 / 6 / 8 / 16 -> 240.4 / 239.7 / 239.1 /
-// 239.2 / 238.9 / 240.5 / 241.9 ms
-#define PSO_GEMM_GROUP_M 4
+  pso_set_error("pso_gemm: tile %d x %d (%d x %d waves, %d stages%s, epilogue %d) is not compiled into this library",
+                p.BM, p.BN, p.WM, p.WN, p.STAGES, p.PIPE ? ", pipelined" : "", p.epi);
+  return PSO_ERR_UNSUPPORTED;
+}
+#undef PSO_TILE
 
-// the variants 37-58 keep the automatic dispatch and flip one of its rules (41 = per-lane epilogue; 37 / 38 = the
-// 256 x 160 8-phase tiles off / forced; 56 = the 256 x 256 TN tiles off; ...); any other non-zero variant forces one tile shape
-static int gemm_auto_variant(int gv_raw) { return (gv_raw >= 37 && gv_raw <= 58) ? 0 : gv_raw; }
-// the workspace split-K forms (pso_gemm_ws / pso_conv2d_ws) under the benchmark knobs: off where a variant forces a
-// tile (38 / 39 / 44: the 8-phase 256 x 160 / 256 x 320 / conv tiles, the tests that pin them), where a raster group
-// is forced, and under variant 52 (the conv split off)
-static bool gemm_ws_allowed() {
-  const int v = g_gemm_variant;
-  return g_gemm_group == 0 && gemm_auto_variant(v) == 0 && v != 38 && v != 39 && v != 44 && v != 52;
+// Launch what the plan says (g.vec_ok / stage_epi / group_m / ws are the plan's)
+static int run_plan(const GemmPlan& p, GemmArgs& g, hipStream_t st) {
+  g.stage_epi = p.stage_epi; g.vec_ok = p.vec_ok; g.group_m = p.group_m;
+  if (p.ws_ks < 2) g.ws = nullptr;
+  switch (p.form) {
+    case GF_NONE: return PSO_OK;
+    case GF_SKINNY:
+      return pso_gemm_skinny_nt(g.M, g.N, g.K1, g.a1, g.lda1, g.b1, g.ldb1, g.alpha, g.out, g.ldo,
+                                g.out_dtype == PSO_F32, g.accumulate, 1, st);
+    case GF_SMALL_CONV:
+      return pso_conv3x3_smallc_run(g.M / (g.conv.H * g.conv.W), g.conv.H, g.conv.W, g.conv.C1, g.N, g.a1, g.b1, g.bias,
+                                    g.out, st);
+    case GF_8P256: return pso_gemm8p_launch(256, p.epi, false, gemm8_args(g), st);
+    case GF_8P160: return pso_gemm8p_launch(160, p.epi, false, gemm8_args(g), st);
+    case GF_8P320: return pso_gemm8p_launch(320, p.epi, false, gemm8_args(g), st);
+    case GF_8P320_CONV: return pso_gemm8p_launch(320, p.epi, true, gemm8_args(g), st);
+    case GF_TILE: break;
+    default: pso_set_error("pso_gemm: bad plan form %d", p.form); return PSO_ERR_UNSUPPORTED;
+  }
+  if (p.ws_ks >= 2) {  // every split stores its partial product; reduced in split order with the epilogue
+    launch_tile(p, g, st, p.ws_ks);
+    const long n4 = (long)g.M * (g.N / 4);
+    gemm_splitk_reduce_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, st>>>(g, p.ws_ks);
+    return pso_check_launch("pso_gemm_ws");
+  }
+  return launch_tile(p, g, st, p.atomic_ks);
 }
 
-static int run_gemm(GemmArgs& g, hipStream_t st) {
-  const int gv_raw = g_gemm_variant;
-  const int gv = gemm_auto_variant(gv_raw);
-  if (g.M <= 0 || g.N <= 0) return PSO_OK;
-  g.group_m = g_gemm_group > 0 ? g_gemm_group : PSO_GEMM_GROUP_M;
-  if (g.tail_group_n > 0 && (g.tail_group_n % 64) != 0) {
+// ws_bytes: the size of the workspace g.ws (pso_gemm_ws / pso_conv2d_ws); small_conv_entry: gemm_plan.h GemmFacts
+static int run_gemm(GemmArgs& g, hipStream_t st, size_t ws_bytes = 0, bool small_conv_entry = false) {
+  GemmFacts f = gemm_facts(g, ws_bytes, small_conv_entry);
+  GemmPlan p = gemm_plan(f, g_gemm_knobs);
+  if (p.form == GF_SMALL_CONV) {  // a failed direct convolution falls back to the GEMM forms
+    if (run_plan(p, g, st) == PSO_OK) return PSO_OK;
+    f.small_conv_entry = false;
+    p = gemm_plan(f, g_gemm_knobs);
+  }
+  if (p.form != GF_NONE && g.tail_group_n > 0 && (g.tail_group_n % 64) != 0) {
     pso_set_error("pso_gemm: tail_group_n must be a multiple of 64");
     return PSO_ERR_ARG;
   }
-  // staged 16-B epilogue for bf16 outputs with 16-B aligned rows (5-10 % on the K = 640 / 1280 projections with
-  // bias + residual, tools/epi_bench.py); variant 41 keeps the per-lane 8-B epilogue (A/B knob)
-  g.stage_epi = gv_raw != 41 && g.out_dtype == PSO_ELEM && al16(g.out) && (g.ldo % 8) == 0 &&
-                (!g.resid || (al16(g.resid) && (g.ldr % 8) == 0));
-  g.vec_ok = (g.ldo % 4) == 0 && (g.out_dtype == PSO_F32 ? al16(g.out) : al8(g.out)) &&
-             (!g.resid || ((g.ldr % 4) == 0 && al8(g.resid))) && (!g.bias || al8(g.bias)) &&
-             (!g.rowbias || (al8(g.rowbias) && (g.ld_rowbias % 4) == 0));
-  const bool bn64_only = g.tail_group_n > 0 && (g.tail_group_n % 128) != 0;  // grouped tail needs BN | group
-  const bool bn256_ok = g.tail_group_n == 0 || (g.tail_group_n % 256) == 0;
-  const long Ktot = (long)g.K1 + (g.a2 ? g.K2 : 0);
-  if (g.batch > 1) {  // batched dense product (the VAE's single-head mid attention): the 2-phase tiles only
-    auto tl = [&](int bm, int bn) { return (long)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn) * g.batch; };
-    if ((g.N % 160) == 0 && tl(128, 160) >= 256) return launch<128, 160, 2, 2, 2>(g, st);
-    if (tl(128, 128) >= 256) return launch<128, 128, 2, 4, 2>(g, st);
-    return launch<64, 64>(g, st);
-  }
-  // deterministic split-K through the caller's workspace (pso_gemm_ws): small M x N, long K
-  if (g.ws) {
-    const SplitPlan sp = gemm_split_plan(g.M, g.N, g.K1, g.K2, g.a2 != nullptr, true);  // entries checked the form
-    if (sp.ks >= 2) {
-      if (sp.bn == 160) launch<128, 160, 2, 2, 2>(g, st, sp.ks);
-      else launch<128, 128, 2, 4, 2>(g, st, sp.ks);
-      const long n4 = (long)g.M * (g.N / 4);
-      gemm_splitk_reduce_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, st>>>(g, sp.ks);
-      return pso_check_launch("pso_gemm_ws");
-    }
-    g.ws = nullptr;
-  }
-  // Skinny N (the LoRA rank-r products): one 16-row x all-N tile per 4-wave block, K split over the waves.
-  if (gv == 0 && !g.conv.mode && !g.a2 && !g.bias && !g.rowbias && !g.resid && g.N <= 128 &&
-      (g.N % 4) == 0 && g.vec_ok && g.M >= 256)
-    return pso_gemm_skinny_nt(g.M, g.N, g.K1, g.a1, g.lda1, g.b1, g.ldb1, g.alpha, g.out, g.ldo,
-                              g.out_dtype == PSO_F32, g.accumulate, 1, st);
-  // Small outputs with a long reduction: split K over blocks, f32 atomics in the epilogue.
-  const bool can_split = g.out_dtype == PSO_F32 && g.accumulate && !g.bias && !g.rowbias && !g.resid &&
-                         !g.conv.mode && g.tail_group_n == 0;
-  if (can_split && (g.M <= 128 || g.N <= 128) && Ktot >= 2048) {
-    const long tiles = (long)((g.M + 63) / 64) * ((g.N + 63) / 64);
-    const long ktiles = (Ktot + BK - 1) / BK;
-    long ks = (512 + tiles - 1) / tiles;
-    if (ks > ktiles / 2) ks = ktiles / 2;
-    if (ks < 1) ks = 1;
-    return launch<64, 64>(g, st, (int)ks);
-  }
-  // 3x3 / stride 1 / pad 1 convolutions (the ResNet convs and their input gradients) on the 8-phase 256 x 320 tiles
-  // (gemm8p.hip CONV form) wherever they fill a round of CUs; variant 43 keeps them on the 2-phase kernel, 44 forces it
-  {
-    const ConvGeom& cv = g.conv;
-    const long hw = (long)cv.Ho * cv.Wo;
-    const bool conv8 = cv.mode == PSO_CONV_NORMAL && cv.ks == 3 && cv.stride == 1 && cv.pad == 1 && cv.H == cv.Ho &&
-                       cv.W == cv.Wo && cv.C2 == 0 && (cv.C1 % 64) == 0 && cv.C1 <= 4096 && (hw % 256) == 0 &&
-                       (cv.H & (cv.H - 1)) == 0 && (cv.W & (cv.W - 1)) == 0 && cv.W >= 8 &&
-                       (g.N % 320) == 0 && !g.a2 && g.out_dtype == PSO_ELEM && !g.accumulate && al16(g.out) &&
-                       (g.ldo % 8) == 0 && (!g.resid || (al16(g.resid) && (g.ldr % 8) == 0)) &&
-                       (!g.bias || al8(g.bias)) && (!g.rowbias || (al8(g.rowbias) && g.rows_per_group == hw)) &&
-                       fits30((long)g.M + 2L * (cv.W + 1), cv.C1) && fits30(g.N, g.ldb1) && al16(g.a1) && al16(g.b1);
-    const long t320c = (long)(g.M / 256) * (g.N / 320);
-    const long min320c = (gv_raw == 46 || gv_raw == 47) ? 256 : 192;
-    if (conv8 && gv_raw != 43 && (gv_raw == 44 || (gv == 0 && t320c >= min320c)))
-      return pso_gemm8p320_conv_run(g.M / (int)hw, cv.H, cv.W, cv.C1, g.a1, g.b1, g.N, g.alpha, g.bias, g.rowbias,
-                                    g.ld_rowbias, g.resid, g.ldr, g.out, g.ldo, g.group_m, st);
-  }
-  // 8-phase 256x256 (gemm8p.hip, wave groups staggered) for dense bf16 GEMMs with N % 256 == 0: LDS-staged 16-B
-  // epilogue, LoRA K-tail, bias / alpha / residual.  Default for N >= 2560 with >= 256 tiles (tools/gemm8_ab.py, one
-  // box: q/k/v 16384 x 3840 x 1280 1071 vs 937 TF/s, ff.out dX 8192 x 5120 x 1280 991 vs 945); N = 1280 keeps 128x160
-  // (1.25 rounds of 256x256 tiles at M = 16384: 805 vs 928).  Variant 30 forces it, 31 keeps it off everywhere.
-  const bool base8 = !g.conv.mode && !g.rowbias && g.out_dtype == PSO_ELEM && !g.accumulate && (g.K1 % 64) == 0 &&
-                     al16(g.a1) && al16(g.b1) && (g.lda1 % 8) == 0 && (g.ldb1 % 8) == 0 && al16(g.out) &&
-                     (g.ldo % 8) == 0 && (!g.resid || (al16(g.resid) && (g.ldr % 8) == 0)) &&
-                     (!g.bias || al8(g.bias)) && fits30(g.M, g.lda1) && fits30(g.N, g.ldb1) &&
-                     (!g.a2 || (fits30(g.tail_m, g.lda2) && fits30(g.N, g.ldb2)));
-  const bool ok8 = base8 && (g.N % 256) == 0 && (!g.a2 || g.tail_group_n == 0 || (g.tail_group_n % 256) == 0);
-  const long t256 = (long)((g.M + 255) / 256) * (g.N / 256);
-  // wide N (>= 2560) whose 256 x 256 tiles leave a partial round while the 256 x 320 ones make whole rounds (C3's
-  // 6144 x 10240 x 1280: 960 vs 768 tiles, 979 vs 1079 TF/s; 24576 x 5120 x 640: 802 vs 832) take the 320 form below;
-  // variant 46 keeps the round-2 rules
-  const bool ok320w = base8 && (g.N % 320) == 0 && g.lda1 == g.ldb1 && (!g.a2 || g.K2 <= 64) &&
-                      (!g.a2 || g.tail_group_n == 0 || (g.tail_group_n % 320) == 0);
-  const long t320w = (long)((g.M + 255) / 256) * (g.N / 320);
-  const bool wide320 = gv == 0 && gv_raw != 46 && ok320w && g.N >= 2560 && (t256 % 256) != 0 && t320w >= 256 &&
-                       (t320w % 256) == 0;
-  // three quarters of a round of 256 x 256 tiles where the 256 x 320 ones leave more CUs idle (C4's 12288 x 1280:
-  // 240 vs 192 tiles, 1056 vs 877-919 TF/s; bs = 1's q/k/v 4096 x 3840: 240 tiles, 938 vs 798 on the 2-phase
-  // tiles; tools/small_m_bench.py); variant 50 keeps the full-round rule
-  const long t320r = (g.N % 320) == 0 ? (long)((g.M + 255) / 256) * (g.N / 320) : 0;
-  const bool part256 = gv == 0 && gv_raw != 50 && t256 >= 192 && t256 < 256 && t256 > t320r;
-  if (ok8 && !wide320 && (gv == 30 || part256 || ((gv == 32 || (gv == 0 && g.N >= 2560)) && t256 >= 256)))
-    return pso_gemm8p_run(0, g.M, g.N, g.K1, g.a1, g.lda1, g.b1, g.ldb1, g.a2, g.lda2, g.K2, g.b2, g.ldb2, g.tail_m,
-                          g.tail_group_n, g.alpha, g.bias, g.resid, g.ldr, g.out, g.ldo, nullptr, 0, 0, nullptr, 0,
-                          g.group_m, st);
-  // 8-phase 256 x 160 (gemm8p.hip) for the N % 160 == 0 widths with at least one round of tiles and a long reduction
-  // (K >= 2560: ff.out 16384 x 1280 x 5120 972 vs 942 TF/s, 32768 x 640 x 5120 1039 vs 910, 65536 x 640 x 2560 823
-  // vs 770); at K = 640 / 1280 the 2-phase 128 x 160 with two co-resident blocks per CU (one block's epilogue beside
-  // the other's main loop) stays ahead (16384 x 1280 x 1280 827 vs 724, tools/shape_prof.py one box).  Variant 37
-  // keeps the 2-phase 128 x 160, 38 forces the 8-phase form wherever it applies.
-  // 8-phase 256 x 320 (gemm8p.hip): every SDXL width is a multiple of 320, and at the UNet's M (256 * 2^k rows) the
-  // tile count is a whole number of 256-CU rounds (N = 1280 at M = 16384: 256 tiles; N = 640 at M = 65536: 512).
-  // Default where it fills at least one round and the reduction is short (K < 2560: the 256 x 160 persistent form
-  // keeps the long ones); at half a round (M = 8192, N = 1280: 128 tiles) the 2-phase 128 x 160 stays ahead
-  // (tools/shape_prof.py, one box: 16384 x 1280 x 1280 + LoRA 922 vs 816 TF/s, 65536 x 640 x 640 + LoRA 700 vs 652,
-  // 65536 x 1920 x 640 + LoRA 849 vs 783; 8192 x 1280 x 1280 + LoRA 574 vs 776).  Variant 39 forces it, 40 keeps it
-  // off.
-  const bool ok320 = base8 && (g.N % 320) == 0 && g.lda1 == g.ldb1 && (!g.a2 || g.K2 <= 64) &&
-                     (!g.a2 || g.tail_group_n == 0 || (g.tail_group_n % 320) == 0);
-  const long t320 = (long)((g.M + 255) / 256) * (g.N / 320);
-  // three quarters of a round already beats the 2-phase tiles (C4's 12288 x 1280 x 5120: 1072 vs 811 TF/s, x 1280:
-  // 875 vs 830; C3's 24576 x 640 x 2560: 1034 vs 725, x 640: 685 vs 612 -- 192 tiles each); half a round does not
-  // (8192 x 1280 x 1280: 574 vs 776).  Variant 46 / 47 keep the full-round rule.
-  const long min320 = (gv_raw == 46 || gv_raw == 47) ? 256 : 192;
-  if (ok320 && gv_raw != 40 && gv_raw != 38 &&
-      (gv_raw == 39 || wide320 ||
-       (gv == 0 && t320 >= min320 && g.N < 2560 && (gv_raw != 42 || Ktot < 2560))))
-    return pso_gemm8p320_run(g.M, g.N, g.K1, g.a1, g.lda1, g.b1, g.ldb1, g.a2, g.lda2, g.K2, g.b2, g.ldb2, g.tail_m,
-                             g.tail_group_n, g.alpha, g.bias, g.resid, g.ldr, g.out, g.ldo, g.group_m, st);
-  const bool ok160 = base8 && (g.N % 160) == 0 && (!g.a2 || g.tail_group_n == 0 || (g.tail_group_n % 160) == 0);
-  const long t160 = (long)((g.M + 255) / 256) * (g.N / 160);
-  if (ok160 && gv_raw != 37 && (gv_raw == 38 || (gv == 0 && t160 >= 256 && Ktot >= 2560)))
-    return pso_gemm8p160_run(g.M, g.N, g.K1, g.a1, g.lda1, g.b1, g.ldb1, g.a2, g.lda2, g.K2, g.b2, g.ldb2, g.tail_m,
-                             g.tail_group_n, g.alpha, g.bias, g.resid, g.ldr, g.out, g.ldo, g.group_m, st);
-  const bool n160 = (g.N % 160) == 0 && (g.tail_group_n == 0 || (g.tail_group_n % 160) == 0);
-#ifdef PSO_BENCH_KNOBS  // forced tile shapes (A/B and tests of the knobs build)
-  if (gv == 4 && bn256_ok) return launch<256, 256, 2, 4, 2>(g, st);
-  if (gv == 5 && !bn64_only) return launch<256, 128, 2, 4, 2>(g, st);
-  if (gv == 1 && !bn64_only) return launch<256, 128, 4, 2, 3>(g, st);
-  if (gv == 2 && !bn64_only) return launch<128, 128, 2, 2, 3>(g, st);
-  if (gv == 3 && !bn64_only) return launch<128, 128>(g, st);
-  if (gv == 6 && !bn64_only) return launch<64, 128>(g, st);
-  if (gv == 7 && bn256_ok) return launch<128, 256, 2, 4, 2>(g, st);
-  if (gv == 8 && !bn64_only) return launch<128, 128, 2, 4, 2>(g, st);
-  if (gv == 10 && bn256_ok) return launch<256, 256, 2, 4, 2, true>(g, st);
-  if (gv == 11 && !bn64_only) return launch<128, 128, 2, 4, 2, true>(g, st);
-  const bool n320 = (g.N % 320) == 0 && (g.tail_group_n == 0 || (g.tail_group_n % 320) == 0);
-  if (gv == 12 && n160) return launch<128, 160, 2, 2, 2>(g, st);
-  if (gv == 14 && n160) return launch<256, 160, 2, 2, 2>(g, st);
-  if (gv == 16 && n160) return launch<256, 160, 2, 2, 2, true>(g, st);
-  if (gv == 17 && n320) return launch<128, 320, 2, 4, 2>(g, st);
-  if (gv == 18 && n320) return launch<256, 320, 2, 4, 2>(g, st);
-  if (gv == 19 && n160) return launch<128, 160, 2, 2, 2, true>(g, st);
-  // small-M tiles (the bs = 1 backward at M = 2048: N = 1280 makes exactly one 256-CU round of 64 x 160 / 128 x 80)
-  if (gv == 20 && n160) return launch<64, 160, 2, 2, 2>(g, st);
-  if (gv == 21 && (g.N % 80) == 0 && (g.tail_group_n % 80) == 0) return launch<128, 80, 4, 1, 2>(g, st);
-  if (gv == 22 && n160) return launch<64, 160, 2, 2, 3>(g, st);
-  // deeper direct-to-LDS rings for the latency-bound short-K small-M products (4 / 5 stages: 3 / 4 K-tiles in flight)
-  if (gv == 23 && n160) return launch<64, 160, 2, 2, 4>(g, st);
-  if (gv == 24 && n160) return launch<64, 160, 2, 2, 5>(g, st);
-  if (gv == 25 && !bn64_only) return launch<64, 64, 2, 2, 4>(g, st);
-  if (gv == 26 && n160) return launch<128, 160, 2, 2, 4>(g, st);
-  if (gv == 27 && !bn64_only) return launch<64, 128, 2, 2, 4>(g, st);
-  if (gv == 28 && !bn64_only) return launch<128, 128, 2, 4, 4>(g, st);
-  if (gv == 29 && !bn64_only) return launch<64, 64, 2, 2, 5>(g, st);
-#endif
-  // Tile choice by occupancy (~2 co-resident 4-wave blocks per CU, 256 CUs): large grids keep 128x128 (best operand
-  // reuse); grids that would leave CUs idle drop to 64x128 / 128x64 / 64x64 (e.g. the L2 projections, M=4096 N=1280,
-  // and the skinny LoRA projections N = r..3r).
-  auto tiles = [&](int bm, int bn) { return (long)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn); };
-  if (g.N <= 64) return launch<64, 64>(g, st);
-  if (bn64_only) return tiles(128, 64) >= 512 ? launch<128, 64>(g, st) : launch<64, 64>(g, st);
-  if (g.M <= 64) return launch<64, 128>(g, st);
-  // 256x256 block tile, 8 waves x (128x64): twice the MFMAs per LDS fragment read; wins once the grid covers the 256
-  // CUs (one 128 KiB-LDS block per CU) and N has no partial 256-column tile; implicit-GEMM convs (long K) already
-  // at half a wave of blocks.  Otherwise 128x128 with 8 waves (64x32 each).  Measured on the UNet shapes at 8 images
-  // (tools/gemm_bench.py): e.g. L2 qkv 8192x3840x1280 713 vs 645 TF/s; L2 proj 8192x1280x1280 531 vs 474.
-  // Very large grids (>= 4 rounds of 256x256 tiles: L1/L2 ff.proj, the 128^2 upsample conv) keep 256x256.  Otherwise
-  // N % 160 == 0 (every SDXL width: 320 | N) takes 128x160 with 4 waves of 64x80: fewer LDS bytes per MFMA than the
-  // 8-wave 128x128 (64x32 wave tiles) and tile counts that divide the 512 co-resident slots (M=8192, N=1280 -> 512
-  // tiles).  tools/gemm_bench.py at 8 images: L2 ff.out 8192x1280x5120 797 -> 1097 TF/s, L2 proj 636 -> 816,
-  // L0/L1/L2 3x3 convs 733/887/795 -> 921/994/1005.
-  if (bn256_ok && (g.N % 256) == 0 && tiles(256, 256) >= 1024) return launch<256, 256, 2, 4, 2>(g, st);
-  // 128 x 160 tiles that leave a quarter of the 512 co-resident slots empty while 128 x 128 ones nearly fill them
-  // (C3's 6144-row L2 products, N = 1280: 384 vs 480 tiles; proj 678 -> 753 TF/s, ff.out 860 -> 971, GEGLU dX
-  // 940 -> 1023, 3x3 conv 802 -> 864): the 8-wave 128 x 128 kernel.  At half the slots (4096 x 1280, the bs=1 LoRA
-  // pass: 256 vs 320 tiles) 128 x 160 stays ahead (step 90.5 vs 93.2 ms).  Variant 46 keeps the 128 x 160 choice.
-  if (gv_raw != 46 && !bn64_only && n160 && tiles(128, 160) >= 384 && tiles(128, 160) < 512 &&
-      tiles(128, 128) <= 512)
-    return launch<128, 128, 2, 4, 2>(g, st);
-  // 128 x 160 tiles that make at most one workgroup per CU while 64 x 160 ones make 1.5-2 (the bs = 1 / GPU pass:
-  // 4096 x 1280 and 8192 x 640 rows; tools/small_m_bench.py, one box: 4096 x 1280 x 5120 837 vs 755 TF/s, x 1280 + LoRA
-  // 649 vs 540, 8192 x 640 x 5120 843 vs 759, x 1920 + LoRA 718 vs 637); variant 48 keeps 128 x 160 there
-  if (gv_raw != 48 && n160 && tiles(128, 160) <= 256 && tiles(64, 160) >= 384) return launch<64, 160, 2, 2, 2>(g, st);
-  // smaller still (M = 2048, N = 1280: 256 tiles of 64 x 160, 640 of 64 x 64), short K (the long ones split K through
-  // a workspace, pso_gemm_ws): variant 49 takes the register-pipelined 8-wave 128 x 128 tiles. They win in isolation
-  // (tools/small_m_bench.py: 2048 x 1280 x 1280 + LoRA 404 vs 319 TF/s) but lose inside the bs = 1 step
-  // (tools/shape_prof.py, one box: 252-256 vs 277 TF/s), so 64 x 64 stays the default there
-#ifdef PSO_BENCH_KNOBS
-  if (gv_raw == 49 && !g.conv.mode && !bn64_only && (g.N % 128) == 0 && tiles(64, 160) <= 256 &&
-      tiles(128, 128) >= 128 && tiles(128, 160) < 256)
-    return launch<128, 128, 2, 4, 2, true>(g, st);
-#endif
-  if (n160 && tiles(128, 160) >= 256) return launch<128, 160, 2, 2, 2>(g, st);
-  if (bn256_ok && (g.N % 256) == 0 && tiles(256, 256) >= (g.conv.mode ? 128 : 256))
-    return launch<256, 256, 2, 4, 2>(g, st);
-  if (tiles(128, 128) >= 256) return launch<128, 128, 2, 4, 2>(g, st);
-  if (tiles(64, 128) >= 512) return (g.N % 128 == 0) ? launch<64, 128>(g, st) : launch<128, 64>(g, st);
-  return launch<64, 64>(g, st);
+  return run_plan(p, g, st);
 }
 
 // =====================================================================================================================
@@ -1498,28 +1298,6 @@ __global__ __launch_bounds__(512, 1) void gemm_tn256_kernel(int M, int I, int J,
   }
 }
 
-// the 256 x 256 TN tiles (variant 56 keeps the 128 x 128 ones): both sides multiples of 256 and the operands within
-// 32-bit buffer offsets.  Returns the slice count: 1 where the tiles alone cover >= 3/4 of the CUs (out += directly);
-// one round of workspace slices of >= 8 K-steps each where the 128 x 128 tiles would run one pass of 256-383
-// workgroups (< 3/4 of the two-per-CU slots, and too many for tn_ws_slices); else 0 = not this kernel.
-// tools/tn_full_bench.py, TF/s 256 vs 128 tiles: 6144 x 1280 x 11520 (225 tiles) 948 / 929 vs 835 / 836, 24576 x 1280
-// x 11520 990 vs 823, the GEGLU 6144 x 10240 x 1280 (200 tiles) 720 / 736 vs 658 / 725, 6144 x 3840 x 1280 (75 tiles x
-// 3 slices) 675 / 683 vs 607 / 616; slices where the 128 x 128 tiles already fill the slots lose (6144 x 1280 x 5120,
-// 100 tiles x 2: 670 vs 752; 6144 x 1280 x 1280, 25 x 10: 411 vs 471): the partials' round trip through HBM.
-static int tn256_slices(int M, int I, int J, long lda, long ldb) {
-  if (g_gemm_variant == 56 || I % 256 || J % 256 || (long)M * lda >= (1L << 30) || (long)M * ldb >= (1L << 30))
-    return 0;
-  const int t256 = (I / 256) * (J / 256);
-  if (t256 >= 192) return 1;
-  const int t128 = (I / 128) * (J / 128);
-  if (t128 < 256 || t128 >= 384) return 0;
-  const int nkt = (M + 63) / 64;
-  int ks = 256 / t256;
-  if (ks > nkt / 8) ks = nkt / 8;
-  if (ks < 2) return 0;
-  const int steps = (nkt + ks - 1) / ks;
-  return (nkt + steps - 1) / steps;
-}
 
 static void tn256_launch(int M, int I, int J, const void* A, long lda, const void* B, long ldb, float alpha, float* out,
                          long ldo, int ks, float* part, int geglu_f, hipStream_t st) {
@@ -1536,85 +1314,123 @@ static void tn256_launch(int M, int I, int J, const void* A, long lda, const voi
                                                                           steps, part, geglu_f);
 }
 
-// split of the full-weight TN product into ks slices of the reduction rows for the workspace form: enough slices for
-// ~1.5 rounds of 128 x 128 tiles over the 256 CUs, each slice >= 8 K-steps (512 rows)
-static int tn_ws_slices(int M, int I, int J) {
-  if (I < 128 || J < 128) return 0;
-  const int t128 = ((I + 127) / 128) * ((J + 127) / 128);
-  if (t128 >= 256) return 0;
-  const int nkt = (M + 63) / 64;
-  int ks = (384 + t128 - 1) / t128;
-  if (ks > nkt / 8) ks = nkt / 8;
-  return ks >= 2 ? ks : 0;
-}
-
-// Deterministic plan of a TN product with a caller-owned workspace (pso_gemm_tn_ws): every split of the reduction
-// rows stores its partial product and the partials are added in split order -- no f32 atomics anywhere.
-//   TNP_RANK:  one side a rank-16/32/64/96 projection -> the rank-r streaming kernel's workspace form
-//   TNP_128:   both sides >= 128 wide -> 128 x 128 tiles, ks slices (the small-weight split of tn_ws_slices, else the
-//              split the atomic form would take)
-//   TNP_64:    the rest -> 64 x 64 tiles, ks slices
-//   TNP_PLAIN: no split: out += directly (deterministic as it stands)
-//   TNP_256:   both sides multiples of 256 with too few tiles for the CUs -> 256 x 256 tiles, one round of slices
-enum { TNP_PLAIN = 0, TNP_RANK = 1, TNP_128 = 2, TNP_64 = 3, TNP_256 = 4 };
-struct TnPlan { int kind, ks, steps; size_t bytes; };
-static bool tn_rank_ok(int r) { return r == 16 || r == 32 || r == 64 || r == 96; }
-static TnPlan tn_plan(int M, int I, int J, long lda, long ldb) {
-  TnPlan p{TNP_PLAIN, 1, 0, 0};
-  if (M <= 0) return p;
-  if ((I % 128 == 0 && tn_rank_ok(J)) || (J % 128 == 0 && tn_rank_ok(I))) {
-    const bool x_is_a = I % 128 == 0 && tn_rank_ok(J);
-    PsoTnRankProblem q{};
-    q.x = (const void*)16; q.u = (const void*)16; q.out = (float*)16; q.ldx = 8; q.ldu = 8;
-    q.ldo = x_is_a ? J : I; q.M = M; q.C = x_is_a ? I : J; q.group_c = 0; q.alpha = 1.f;
-    p.kind = TNP_RANK;
-    p.bytes = pso_gemm_tn_rank_batch_ws_bytes(x_is_a ? J : I, x_is_a ? 0 : 1, 1, &q);
-    return p;
-  }
-  const int nkt = (M + 63) / 64;
-  const int ks256 = tn256_slices(M, I, J, lda, ldb);
-  if (ks256 == 1) return p;  // the direct 256 x 256 form (pso_gemm_tn_grouped)
-  if (ks256 >= 2) {
-    p.kind = TNP_256;
-    p.ks = ks256;
-    p.steps = (nkt + ks256 - 1) / ks256;
-    p.bytes = (size_t)ks256 * I * J * sizeof(float);
-    return p;
-  }
-  if (I >= 128 && J >= 128 && (long)M * lda < (1L << 30) && (long)M * ldb < (1L << 30)) {
-    int ks = tn_ws_slices(M, I, J);
-    if (!ks) {  // the split the atomic form takes (pso_gemm_tn_grouped): ks <= M / 16384 where it yields >= 128 blocks
-      const int t128 = ((I + 127) / 128) * ((J + 127) / 128);
-      ks = (512 + t128 - 1) / t128;
-      if (ks > M / 16384) ks = M / 16384;
-      if (ks < 1) ks = 1;
-      const int st0 = (nkt + ks - 1) / ks;
-      ks = (nkt + st0 - 1) / st0;
-      if (t128 * ks < 128) ks = 0;  // the 64 x 64 kernel's domain
-    }
-    if (ks >= 2) {
-      p.kind = TNP_128;
-      p.steps = (nkt + ks - 1) / ks;
-      p.ks = (nkt + p.steps - 1) / p.steps;
-      p.bytes = (size_t)p.ks * I * J * sizeof(float);
-      return p;
-    }
-    if (ks == 1) return p;
-  }
-  const int tiles = ((I + 63) / 64) * ((J + 63) / 64);
-  int ks = (160 + tiles - 1) / tiles;
-  if (ks > nkt) ks = nkt;
-  if (ks >= 2) {
-    p.kind = TNP_64;
-    p.ks = ks;
-    p.bytes = (size_t)ks * I * J * sizeof(float);
-  }
-  return p;
+// the workspace a TN plan needs (gemm_plan.h tn_plan with have_ws; 0: none)
+static size_t tn_plan_ws_bytes(const TnPlan& p, int M, int I, int J) {
+  if (!p.ws) return 0;
+  if (p.kind != TNP_RANK) return (size_t)p.ks * I * J * sizeof(float);
+  PsoTnRankProblem q{};
+  q.x = (const void*)16; q.u = (const void*)16; q.out = (float*)16; q.ldx = 8; q.ldu = 8;
+  q.ldo = p.swap ? I : J; q.M = M; q.C = p.swap ? J : I; q.group_c = 0; q.alpha = 1.f;
+  return pso_gemm_tn_rank_batch_ws_bytes(p.rank, p.swap ? 1 : 0, 1, &q);
 }
 
 extern "C" {
 
-size_t pso_gemm_tn_ws_bytes(int M, int I, int J) { return tn_plan(M, I, J, I, J).bytes; }
+size_t pso_gemm_tn_ws_bytes(int M, int I, int J) {
+  if (M <= 0) return 0;
+  GemmKnobs k = g_gemm_knobs;
+  k.tn_split = 0;  // the size does not follow the split knob; pso_gemm_tn_ws leaves the workspace unused under it
+  return tn_plan_ws_bytes(tn_plan(M, I, J, I, J, 0, true, k), M, I, J);
+}
+
+}  // extern "C"
+
+// the tile kernels of a TN plan: part = the workspace of the plan's slices, or null (out += directly / f32 atomics)
+static void tn_launch_tiles(const TnPlan& p, int M, int I, int J, const void* A, long lda, const void* B, long ldb,
+                            float alpha, float* out, long ldo, float* part, hipStream_t st) {
+  if (p.kind == TNP_256) {
+    tn256_launch(M, I, J, A, lda, B, ldb, alpha, out, ldo, p.ks, part, 0, st);
+  } else if (p.kind == TNP_128) {
+    const int t128 = ((I + 127) / 128) * ((J + 127) / 128);
+    pso_note_kernel("gemm_tn128_kernel");
+    gemm_tn128_kernel<<<dim3(t128, p.ks), 256, 0, st>>>(M, I, J, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, alpha,
+                                                        out, ldo, p.steps, part);
+  } else {
+    const int tiles = ((I + 63) / 64) * ((J + 63) / 64);
+    pso_note_kernel("gemm_tn_kernel");
+    gemm_tn_kernel<<<dim3(tiles, p.ks), 256, 0, st>>>(M, I, J, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, alpha,
+                                                      out, ldo, part);
+  }
+}
+
+// Argument checks and GemmArgs of pso_gemm / pso_gemm_ws (who = the entry's name in the messages)
+static int gemm_entry_args(const char* who, GemmArgs& g, int M, int N, const void* a1, long lda1, int K1,
+                           const void* b1, long ldb1, const void* a2, long lda2, int K2, const void* b2, long ldb2,
+                           float alpha, const void* bias, const void* rowbias, long ld_rowbias, int rows_per_group,
+                           const void* resid, long ldr, void* out, long ldo, int out_dtype, int accumulate,
+                           int tail_group_n, int tail_rows) {
+  PSO_ARG_CHECK(M >= 0 && N >= 0 && K1 >= 0 && (K1 % 8) == 0, "%s: need K1 %% 8 == 0 (K1=%d)", who, K1);
+  PSO_ARG_CHECK(a1 && b1 && out, "%s: null operand", who);
+  PSO_ARG_CHECK(al16(a1) && al16(b1) && (lda1 % 8) == 0 && (ldb1 % 8) == 0, "%s: A1/B1 must be 16-B aligned rows", who);
+  PSO_ARG_CHECK(!a2 || (b2 && (K2 % 8) == 0 && al16(a2) && al16(b2) && (lda2 % 8) == 0 && (ldb2 % 8) == 0),
+                "%s: bad second operand", who);
+  PSO_DTYPE_CHECK(out_dtype, who);
+  PSO_ARG_CHECK((long)M * lda1 < 0x7fffffffL && (long)N * ldb1 < 0x7fffffffL,
+                "%s: operand spans more than 2^31 elements", who);
+  PSO_ARG_CHECK(!accumulate || out_dtype == PSO_F32, "%s: accumulate needs f32 output", who);
+  PSO_ARG_CHECK(!rowbias || rows_per_group > 0, "%s: rowbias needs rows_per_group > 0", who);
+  g.a1 = (const bf16_t*)a1; g.lda1 = lda1; g.K1 = K1;
+  g.b1 = (const bf16_t*)b1; g.ldb1 = ldb1;
+  g.a2 = (const bf16_t*)a2; g.lda2 = lda2; g.K2 = a2 ? K2 : 0;
+  g.b2 = (const bf16_t*)b2; g.ldb2 = ldb2;
+  g.tail_group_n = a2 ? tail_group_n : 0;
+  g.tail_m = (tail_rows > 0 && tail_rows < M) ? tail_rows : M;
+  g.M = M; g.N = N;
+  g.alpha = alpha;
+  g.bias = (const bf16_t*)bias;
+  g.rowbias = (const bf16_t*)rowbias; g.ld_rowbias = ld_rowbias; g.rows_per_group = rows_per_group > 0 ? rows_per_group : 1;
+  g.resid = (const bf16_t*)resid; g.ldr = ldr;
+  g.out = out; g.ldo = ldo; g.out_dtype = out_dtype; g.accumulate = accumulate;
+  return PSO_OK;
+}
+
+// Argument checks and GemmArgs of pso_conv2d / pso_conv2d_ws
+static int conv_entry_args(const char* who, GemmArgs& g, int mode, int B, const void* src1, int C1, const void* src2,
+                           int C2, int H, int W, int Ho, int Wo, int ks, int stride, int pad, const void* weight,
+                           int Cout, const void* a2, long lda2, int K2, const void* b2, long ldb2, float alpha,
+                           const void* bias, const void* rowbias, long ld_rowbias, const void* resid, long ldr,
+                           void* out, long ldo, int out_dtype, int accumulate) {
+  PSO_ARG_CHECK(mode == PSO_CONV_NORMAL || mode == PSO_CONV_UP2 || mode == PSO_CONV_T2, "%s: bad mode", who);
+  PSO_ARG_CHECK(src1 && weight && out, "%s: null operand", who);
+  PSO_ARG_CHECK((C1 % 64) == 0 && (C2 % 64) == 0 && (C2 == 0 || src2),
+                "%s: channel sources must be multiples of 64 (C1=%d C2=%d); use im2col for small C", who, C1, C2);
+  PSO_ARG_CHECK(al16(src1) && (!src2 || al16(src2)) && al16(weight), "%s: alignment", who);
+  PSO_ARG_CHECK(ks == 1 || ks == 3, "%s: ks must be 1 or 3", who);
+  PSO_ARG_CHECK(mode != PSO_CONV_UP2 || (Ho == 2 * H && Wo == 2 * W && stride == 1), "%s: UP2 geometry", who);
+  PSO_ARG_CHECK(!a2 || ((K2 % 8) == 0 && b2 && al16(a2) && al16(b2)), "%s: bad second operand", who);
+  PSO_DTYPE_CHECK(out_dtype, who);
+  PSO_ARG_CHECK(!accumulate || out_dtype == PSO_F32, "%s: accumulate needs f32 output", who);
+  const int Ct = C1 + C2;
+  g.a1 = (const bf16_t*)src1; g.lda1 = 0; g.K1 = ks * ks * Ct;
+  g.b1 = (const bf16_t*)weight; g.ldb1 = g.K1;
+  g.a2 = (const bf16_t*)a2; g.lda2 = lda2; g.K2 = a2 ? K2 : 0;
+  g.b2 = (const bf16_t*)b2; g.ldb2 = ldb2;
+  g.M = B * Ho * Wo; g.N = Cout;
+  g.tail_m = g.M;
+  g.conv.mode = mode; g.conv.src2 = (const bf16_t*)src2; g.conv.C1 = C1; g.conv.C2 = C2;
+  g.conv.H = H; g.conv.W = W; g.conv.Ho = Ho; g.conv.Wo = Wo; g.conv.ks = ks; g.conv.stride = stride; g.conv.pad = pad;
+  g.alpha = alpha;
+  g.bias = (const bf16_t*)bias;
+  g.rowbias = (const bf16_t*)rowbias; g.ld_rowbias = ld_rowbias; g.rows_per_group = Ho * Wo;
+  g.resid = (const bf16_t*)resid; g.ldr = ldr;
+  g.out = out; g.ldo = ldo; g.out_dtype = out_dtype; g.accumulate = accumulate;
+  return PSO_OK;
+}
+
+// GemmArgs of pso_gemm_batched (dense, no epilogue operands)
+static GemmArgs batched_args(int batch, int M, int N, int K, const void* a, long lda, long stride_a, const void* b,
+                             long ldb, long stride_b, float alpha, void* out, long ldo, long stride_o, int out_dtype) {
+  GemmArgs g{};
+  g.a1 = (const bf16_t*)a; g.lda1 = lda; g.K1 = K;
+  g.b1 = (const bf16_t*)b; g.ldb1 = ldb;
+  g.M = M; g.N = N; g.tail_m = M;
+  g.alpha = alpha; g.rows_per_group = 1;
+  g.out = out; g.ldo = ldo; g.out_dtype = out_dtype;
+  g.bat_a = stride_a; g.bat_b = stride_b; g.bat_o = stride_o; g.batch = batch;
+  return g;
+}
+
+extern "C" {
 
 int pso_gemm_tn_ws(int M, int I, int J, const void* A, long lda, const void* B, long ldb, float alpha, float* out,
                    long ldo, void* ws, size_t ws_bytes, void* stream) {
@@ -1624,106 +1440,50 @@ int pso_gemm_tn_ws(int M, int I, int J, const void* A, long lda, const void* B, 
                 "pso_gemm_tn_ws: operands need 16-B aligned rows and I, J multiples of 8");
   if (M == 0) return PSO_OK;
   const hipStream_t st = (hipStream_t)stream;
-  const TnPlan p = tn_plan(M, I, J, lda, ldb);
-  const bool ws_ok = ws && p.bytes && ws_bytes >= p.bytes && (((uintptr_t)ws) & 15) == 0 && g_tn_split == 0;
-  if (p.kind == TNP_RANK && ws_ok) {
-    const bool x_is_a = I % 128 == 0 && tn_rank_ok(J);
+  const TnPlan p = tn_plan(M, I, J, lda, ldb, 0, ws && al16(ws), g_gemm_knobs);
+  const size_t need = tn_plan_ws_bytes(p, M, I, J);
+  // without a workspace that holds every slice: the forms of pso_gemm_tn
+  if (!need || ws_bytes < need) return pso_gemm_tn_grouped(M, I, J, A, lda, B, ldb, alpha, out, ldo, 0, stream);
+  if (p.kind == TNP_RANK) {
     PsoTnRankProblem q{};
-    q.x = x_is_a ? A : B; q.ldx = x_is_a ? lda : ldb;
-    q.u = x_is_a ? B : A; q.ldu = x_is_a ? ldb : lda;
-    q.out = out; q.ldo = ldo; q.M = M; q.C = x_is_a ? I : J; q.group_c = 0; q.alpha = alpha;
-    return pso_gemm_tn_rank_batch_ws(x_is_a ? J : I, x_is_a ? 0 : 1, 1, &q, ws, ws_bytes, stream);
+    q.x = p.swap ? B : A; q.ldx = p.swap ? ldb : lda;
+    q.u = p.swap ? A : B; q.ldu = p.swap ? lda : ldb;
+    q.out = out; q.ldo = ldo; q.M = M; q.C = p.swap ? J : I; q.group_c = 0; q.alpha = alpha;
+    return pso_gemm_tn_rank_batch_ws(p.rank, p.swap ? 1 : 0, 1, &q, ws, ws_bytes, stream);
   }
-  if ((p.kind == TNP_128 || p.kind == TNP_64 || p.kind == TNP_256) && ws_ok) {
-    const long n4 = (long)I * J / 4;
-    if (p.kind == TNP_256) {
-      tn256_launch(M, I, J, A, lda, B, ldb, alpha, out, ldo, p.ks, (float*)ws, 0, st);
-    } else if (p.kind == TNP_128) {
-      const int t128 = ((I + 127) / 128) * ((J + 127) / 128);
-      pso_note_kernel("gemm_tn128_kernel");
-      gemm_tn128_kernel<<<dim3(t128, p.ks), 256, 0, st>>>(M, I, J, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, alpha,
-                                                          out, ldo, p.steps, (float*)ws);
-    } else {
-      const int tiles = ((I + 63) / 64) * ((J + 63) / 64);
-      pso_note_kernel("gemm_tn_kernel");
-      gemm_tn_kernel<<<dim3(tiles, p.ks), 256, 0, st>>>(M, I, J, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, alpha,
-                                                        out, ldo, (float*)ws);
-    }
-    tn_reduce_slices_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, st>>>(I, J, p.ks, (const float*)ws, out, ldo);
-    return pso_check_launch("pso_gemm_tn_ws");
-  }
-  return pso_gemm_tn_grouped(M, I, J, A, lda, B, ldb, alpha, out, ldo, 0, stream);
+  tn_launch_tiles(p, M, I, J, A, lda, B, ldb, alpha, out, ldo, (float*)ws, st);
+  const long n4 = (long)I * J / 4;
+  tn_reduce_slices_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, st>>>(I, J, p.ks, (const float*)ws, out, ldo);
+  return pso_check_launch("pso_gemm_tn_ws");
 }
 
 int pso_gemm(int M, int N, const void* a1, long lda1, int K1, const void* b1, long ldb1, const void* a2, long lda2,
              int K2, const void* b2, long ldb2, float alpha, const void* bias, const void* rowbias, long ld_rowbias,
              int rows_per_group, const void* resid, long ldr, void* out, long ldo, int out_dtype, int accumulate,
              int tail_group_n, int tail_rows, void* stream) {
-  PSO_ARG_CHECK(M >= 0 && N >= 0 && K1 >= 0 && (K1 % 8) == 0, "pso_gemm: need K1 %% 8 == 0 (K1=%d)", K1);
-  PSO_ARG_CHECK(a1 && b1 && out, "pso_gemm: null operand");
-  PSO_ARG_CHECK(al16(a1) && al16(b1) && (lda1 % 8) == 0 && (ldb1 % 8) == 0, "pso_gemm: A1/B1 must be 16-B aligned rows");
-  PSO_ARG_CHECK(!a2 || (b2 && (K2 % 8) == 0 && al16(a2) && al16(b2) && (lda2 % 8) == 0 && (ldb2 % 8) == 0),
-                "pso_gemm: bad second operand");
-  PSO_DTYPE_CHECK(out_dtype, "pso_gemm");
-  PSO_ARG_CHECK((long)M * lda1 < 0x7fffffffL && (long)N * ldb1 < 0x7fffffffL,
-                "pso_gemm: operand spans more than 2^31 elements");
-  PSO_ARG_CHECK(!accumulate || out_dtype == PSO_F32, "pso_gemm: accumulate needs f32 output");
-  PSO_ARG_CHECK(!rowbias || rows_per_group > 0, "pso_gemm: rowbias needs rows_per_group > 0");
   GemmArgs g{};
-  g.a1 = (const bf16_t*)a1; g.lda1 = lda1; g.K1 = K1;
-  g.b1 = (const bf16_t*)b1; g.ldb1 = ldb1;
-  g.a2 = (const bf16_t*)a2; g.lda2 = lda2; g.K2 = a2 ? K2 : 0;
-  g.b2 = (const bf16_t*)b2; g.ldb2 = ldb2;
-  g.tail_group_n = a2 ? tail_group_n : 0;
-  g.tail_m = (tail_rows > 0 && tail_rows < M) ? tail_rows : M;
-  g.M = M; g.N = N;
-  g.alpha = alpha;
-  g.bias = (const bf16_t*)bias;
-  g.rowbias = (const bf16_t*)rowbias; g.ld_rowbias = ld_rowbias; g.rows_per_group = rows_per_group > 0 ? rows_per_group : 1;
-  g.resid = (const bf16_t*)resid; g.ldr = ldr;
-  g.out = out; g.ldo = ldo; g.out_dtype = out_dtype; g.accumulate = accumulate;
-  return run_gemm(g, (hipStream_t)stream);
+  const int rc = gemm_entry_args("pso_gemm", g, M, N, a1, lda1, K1, b1, ldb1, a2, lda2, K2, b2, ldb2, alpha, bias,
+                                 rowbias, ld_rowbias, rows_per_group, resid, ldr, out, ldo, out_dtype, accumulate,
+                                 tail_group_n, tail_rows);
+  return rc != PSO_OK ? rc : run_gemm(g, (hipStream_t)stream);
 }
 
 size_t pso_gemm_ws_bytes(int M, int N, int K1, int K2) {
-  const SplitPlan sp = gemm_split_plan(M, N, K1, K2, K2 > 0, true);
+  const SplitPlan sp = gemm_split_plan(M, N, K1, K2, K2 > 0, g_gemm_knobs);
   return sp.ks >= 2 ? (size_t)sp.ks * M * N * sizeof(float) : 0;
 }
 
+// the workspace form applies when the plan splits and the caller's workspace holds every split; else pso_gemm
 int pso_gemm_ws(int M, int N, const void* a1, long lda1, int K1, const void* b1, long ldb1, const void* a2, long lda2,
                 int K2, const void* b2, long ldb2, float alpha, const void* bias, const void* rowbias, long ld_rowbias,
                 int rows_per_group, const void* resid, long ldr, void* out, long ldo, int out_dtype, int accumulate,
                 int tail_group_n, int tail_rows, void* ws, size_t ws_bytes, void* stream) {
-  PSO_ARG_CHECK(M >= 0 && N >= 0 && K1 >= 0 && (K1 % 8) == 0, "pso_gemm_ws: need K1 %% 8 == 0 (K1=%d)", K1);
-  PSO_ARG_CHECK(a1 && b1 && out, "pso_gemm_ws: null operand");
-  PSO_ARG_CHECK(al16(a1) && al16(b1) && (lda1 % 8) == 0 && (ldb1 % 8) == 0, "pso_gemm_ws: A1/B1 must be 16-B aligned rows");
-  PSO_ARG_CHECK(!a2 || (b2 && (K2 % 8) == 0 && al16(a2) && al16(b2) && (lda2 % 8) == 0 && (ldb2 % 8) == 0),
-                "pso_gemm_ws: bad second operand");
-  PSO_DTYPE_CHECK(out_dtype, "pso_gemm_ws");
-  PSO_ARG_CHECK((long)M * lda1 < 0x7fffffffL && (long)N * ldb1 < 0x7fffffffL,
-                "pso_gemm_ws: operand spans more than 2^31 elements");
-  PSO_ARG_CHECK(!accumulate || out_dtype == PSO_F32, "pso_gemm_ws: accumulate needs f32 output");
-  PSO_ARG_CHECK(!rowbias || rows_per_group > 0, "pso_gemm_ws: rowbias needs rows_per_group > 0");
   GemmArgs g{};
-  g.a1 = (const bf16_t*)a1; g.lda1 = lda1; g.K1 = K1;
-  g.b1 = (const bf16_t*)b1; g.ldb1 = ldb1;
-  g.a2 = (const bf16_t*)a2; g.lda2 = lda2; g.K2 = a2 ? K2 : 0;
-  g.b2 = (const bf16_t*)b2; g.ldb2 = ldb2;
-  g.tail_group_n = a2 ? tail_group_n : 0;
-  g.tail_m = (tail_rows > 0 && tail_rows < M) ? tail_rows : M;
-  g.M = M; g.N = N;
-  g.alpha = alpha;
-  g.bias = (const bf16_t*)bias;
-  g.rowbias = (const bf16_t*)rowbias; g.ld_rowbias = ld_rowbias; g.rows_per_group = rows_per_group > 0 ? rows_per_group : 1;
-  g.resid = (const bf16_t*)resid; g.ldr = ldr;
-  g.out = out; g.ldo = ldo; g.out_dtype = out_dtype; g.accumulate = accumulate;
-  // the workspace form applies when the plan splits and the caller's workspace holds every split; else pso_gemm
-  const SplitPlan sp = gemm_split_plan(M, N, K1, a2 ? K2 : 0, a2 != nullptr, true);
-  const bool ok = ws && (((uintptr_t)ws) & 15) == 0 && sp.ks >= 2 && ws_bytes >= (size_t)sp.ks * M * N * sizeof(float) &&
-                  (ldo % 4) == 0 && (out_dtype == PSO_F32 ? al16(out) : al8(out)) && (g.tail_group_n % sp.bn) == 0 &&
-                  gemm_ws_allowed();
-  g.ws = ok ? (float*)ws : nullptr;
-  return run_gemm(g, (hipStream_t)stream);
+  const int rc = gemm_entry_args("pso_gemm_ws", g, M, N, a1, lda1, K1, b1, ldb1, a2, lda2, K2, b2, ldb2, alpha, bias,
+                                 rowbias, ld_rowbias, rows_per_group, resid, ldr, out, ldo, out_dtype, accumulate,
+                                 tail_group_n, tail_rows);
+  g.ws = (float*)ws;
+  return rc != PSO_OK ? rc : run_gemm(g, (hipStream_t)stream, ws_bytes);
 }
 
 int pso_gemm_batched(int batch, int M, int N, int K, const void* a, long lda, long stride_a, const void* b, long ldb,
@@ -1735,13 +1495,7 @@ int pso_gemm_batched(int batch, int M, int N, int K, const void* a, long lda, lo
   PSO_DTYPE_CHECK(out_dtype, "pso_gemm_batched");
   PSO_ARG_CHECK((long)M * lda < 0x7fffffffL && (long)N * ldb < 0x7fffffffL,
                 "pso_gemm_batched: one operand spans more than 2^31 elements");
-  GemmArgs g{};
-  g.a1 = (const bf16_t*)a; g.lda1 = lda; g.K1 = K;
-  g.b1 = (const bf16_t*)b; g.ldb1 = ldb;
-  g.M = M; g.N = N; g.tail_m = M;
-  g.alpha = alpha; g.rows_per_group = 1;
-  g.out = out; g.ldo = ldo; g.out_dtype = out_dtype;
-  g.bat_a = stride_a; g.bat_b = stride_b; g.bat_o = stride_o; g.batch = batch;
+  GemmArgs g = batched_args(batch, M, N, K, a, lda, stride_a, b, ldb, stride_b, alpha, out, ldo, stride_o, out_dtype);
   return run_gemm(g, (hipStream_t)stream);
 }
 
@@ -1749,85 +1503,32 @@ int pso_conv2d(int mode, int B, const void* src1, int C1, const void* src2, int 
                int ks, int stride, int pad, const void* weight, int Cout, const void* a2, long lda2, int K2,
                const void* b2, long ldb2, float alpha, const void* bias, const void* rowbias, long ld_rowbias,
                const void* resid, long ldr, void* out, long ldo, int out_dtype, int accumulate, void* stream) {
-  PSO_ARG_CHECK(mode == PSO_CONV_NORMAL || mode == PSO_CONV_UP2 || mode == PSO_CONV_T2, "pso_conv2d: bad mode");
-  PSO_ARG_CHECK(src1 && weight && out, "pso_conv2d: null operand");
-  PSO_ARG_CHECK((C1 % 64) == 0 && (C2 % 64) == 0 && (C2 == 0 || src2),
-                "pso_conv2d: channel sources must be multiples of 64 (C1=%d C2=%d); use im2col for small C", C1, C2);
-  PSO_ARG_CHECK(al16(src1) && (!src2 || al16(src2)) && al16(weight), "pso_conv2d: alignment");
-  PSO_ARG_CHECK(ks == 1 || ks == 3, "pso_conv2d: ks must be 1 or 3");
-  PSO_ARG_CHECK(mode != PSO_CONV_UP2 || (Ho == 2 * H && Wo == 2 * W && stride == 1), "pso_conv2d: UP2 geometry");
-  PSO_ARG_CHECK(!a2 || ((K2 % 8) == 0 && b2 && al16(a2) && al16(b2)), "pso_conv2d: bad second operand");
-  PSO_DTYPE_CHECK(out_dtype, "pso_conv2d");
-  PSO_ARG_CHECK(!accumulate || out_dtype == PSO_F32, "pso_conv2d: accumulate needs f32 output");
-  // Cout <= 3 (the VAE decoder's conv_out to RGB): a direct convolution instead of an N = 3 GEMM padded to 64-column
-  // MFMA tiles (conv_small.hip; 1024^2: 1.34 ms -> see DESIGN §4 / profiles/r06_vae_conv_out_ab.log)
-  if (mode == PSO_CONV_NORMAL && ks == 3 && stride == 1 && pad == 1 && Ho == H && Wo == W && C2 == 0 && !a2 &&
-      !rowbias && !resid && alpha == 1.f && out_dtype == PSO_ELEM && !accumulate && ldo == Cout && Cout <= 3 &&
-      pso_conv3x3_smallc_run(B, H, W, C1, Cout, src1, weight, bias, out, (hipStream_t)stream) == PSO_OK)
-    return PSO_OK;
   GemmArgs g{};
-  const int Ct = C1 + C2;
-  g.a1 = (const bf16_t*)src1; g.lda1 = 0; g.K1 = ks * ks * Ct;
-  g.b1 = (const bf16_t*)weight; g.ldb1 = g.K1;
-  g.a2 = (const bf16_t*)a2; g.lda2 = lda2; g.K2 = a2 ? K2 : 0;
-  g.b2 = (const bf16_t*)b2; g.ldb2 = ldb2;
-  g.M = B * Ho * Wo; g.N = Cout;
-  g.tail_m = g.M;
-  g.conv.mode = mode; g.conv.src2 = (const bf16_t*)src2; g.conv.C1 = C1; g.conv.C2 = C2;
-  g.conv.H = H; g.conv.W = W; g.conv.Ho = Ho; g.conv.Wo = Wo; g.conv.ks = ks; g.conv.stride = stride; g.conv.pad = pad;
-  g.alpha = alpha;
-  g.bias = (const bf16_t*)bias;
-  g.rowbias = (const bf16_t*)rowbias; g.ld_rowbias = ld_rowbias; g.rows_per_group = Ho * Wo;
-  g.resid = (const bf16_t*)resid; g.ldr = ldr;
-  g.out = out; g.ldo = ldo; g.out_dtype = out_dtype; g.accumulate = accumulate;
-  return run_gemm(g, (hipStream_t)stream);
+  const int rc = conv_entry_args("pso_conv2d", g, mode, B, src1, C1, src2, C2, H, W, Ho, Wo, ks, stride, pad, weight,
+                                 Cout, a2, lda2, K2, b2, ldb2, alpha, bias, rowbias, ld_rowbias, resid, ldr, out, ldo,
+                                 out_dtype, accumulate);
+  // only this entry takes the direct small-Cout convolution (gemm_plan.h GF_SMALL_CONV)
+  return rc != PSO_OK ? rc : run_gemm(g, (hipStream_t)stream, 0, alpha == 1.f && ldo == Cout);
 }
 
 size_t pso_conv2d_ws_bytes(int B, int Ho, int Wo, int Cout, int K1, int K2) {
   const long M = (long)B * Ho * Wo;
   if (M <= 0 || M > 0x7fffffffL) return 0;
-  const SplitPlan sp = gemm_split_plan((int)M, Cout, K1, K2, K2 > 0, true);
-  return sp.ks >= 2 ? (size_t)sp.ks * M * Cout * sizeof(float) : 0;
+  return pso_gemm_ws_bytes((int)M, Cout, K1, K2);
 }
 
+// the workspace form applies when the plan splits and the workspace holds every split; else the plain conv
 int pso_conv2d_ws(int mode, int B, const void* src1, int C1, const void* src2, int C2, int H, int W, int Ho, int Wo,
                   int ks, int stride, int pad, const void* weight, int Cout, const void* a2, long lda2, int K2,
                   const void* b2, long ldb2, float alpha, const void* bias, const void* rowbias, long ld_rowbias,
                   const void* resid, long ldr, void* out, long ldo, int out_dtype, int accumulate, void* ws,
                   size_t ws_bytes, void* stream) {
-  PSO_ARG_CHECK(mode == PSO_CONV_NORMAL || mode == PSO_CONV_UP2 || mode == PSO_CONV_T2, "pso_conv2d_ws: bad mode");
-  PSO_ARG_CHECK(src1 && weight && out, "pso_conv2d_ws: null operand");
-  PSO_ARG_CHECK((C1 % 64) == 0 && (C2 % 64) == 0 && (C2 == 0 || src2),
-                "pso_conv2d_ws: channel sources must be multiples of 64 (C1=%d C2=%d)", C1, C2);
-  PSO_ARG_CHECK(al16(src1) && (!src2 || al16(src2)) && al16(weight), "pso_conv2d_ws: alignment");
-  PSO_ARG_CHECK(ks == 1 || ks == 3, "pso_conv2d_ws: ks must be 1 or 3");
-  PSO_ARG_CHECK(mode != PSO_CONV_UP2 || (Ho == 2 * H && Wo == 2 * W && stride == 1), "pso_conv2d_ws: UP2 geometry");
-  PSO_ARG_CHECK(!a2 || ((K2 % 8) == 0 && b2 && al16(a2) && al16(b2)), "pso_conv2d_ws: bad second operand");
-  PSO_DTYPE_CHECK(out_dtype, "pso_conv2d_ws");
-  PSO_ARG_CHECK(!accumulate || out_dtype == PSO_F32, "pso_conv2d_ws: accumulate needs f32 output");
   GemmArgs g{};
-  const int Ct = C1 + C2;
-  g.a1 = (const bf16_t*)src1; g.lda1 = 0; g.K1 = ks * ks * Ct;
-  g.b1 = (const bf16_t*)weight; g.ldb1 = g.K1;
-  g.a2 = (const bf16_t*)a2; g.lda2 = lda2; g.K2 = a2 ? K2 : 0;
-  g.b2 = (const bf16_t*)b2; g.ldb2 = ldb2;
-  g.M = B * Ho * Wo; g.N = Cout;
-  g.tail_m = g.M;
-  g.conv.mode = mode; g.conv.src2 = (const bf16_t*)src2; g.conv.C1 = C1; g.conv.C2 = C2;
-  g.conv.H = H; g.conv.W = W; g.conv.Ho = Ho; g.conv.Wo = Wo; g.conv.ks = ks; g.conv.stride = stride; g.conv.pad = pad;
-  g.alpha = alpha;
-  g.bias = (const bf16_t*)bias;
-  g.rowbias = (const bf16_t*)rowbias; g.ld_rowbias = ld_rowbias; g.rows_per_group = Ho * Wo;
-  g.resid = (const bf16_t*)resid; g.ldr = ldr;
-  g.out = out; g.ldo = ldo; g.out_dtype = out_dtype; g.accumulate = accumulate;
-  // the workspace form applies when the plan splits and the workspace holds every split; else the plain conv
-  const SplitPlan sp = gemm_split_plan(g.M, g.N, g.K1, g.K2, g.a2 != nullptr, true);
-  const bool ok = ws && (((uintptr_t)ws) & 15) == 0 && sp.ks >= 2 && ws_bytes >= (size_t)sp.ks * g.M * g.N * sizeof(float) &&
-                  (ldo % 4) == 0 && (out_dtype == PSO_F32 ? al16(out) : al8(out)) && (g.N % 4) == 0 &&
-                  (!resid || ((ldr % 4) == 0 && al8(resid))) && (!rowbias || (ld_rowbias % 4) == 0) &&
-                  gemm_ws_allowed();
-  g.ws = ok ? (float*)ws : nullptr;
-  return run_gemm(g, (hipStream_t)stream);
+  const int rc = conv_entry_args("pso_conv2d_ws", g, mode, B, src1, C1, src2, C2, H, W, Ho, Wo, ks, stride, pad, weight,
+                                 Cout, a2, lda2, K2, b2, ldb2, alpha, bias, rowbias, ld_rowbias, resid, ldr, out, ldo,
+                                 out_dtype, accumulate);
+  g.ws = (float*)ws;
+  return rc != PSO_OK ? rc : run_gemm(g, (hipStream_t)stream, ws_bytes);
 }
 
 int pso_gemm_geglu(int M, int N, const void* a, long lda, int K, const void* w, long ldw, const void* bias, void* out,
@@ -1846,32 +1547,9 @@ int pso_gemm_geglu(int M, int N, const void* a, long lda, int K, const void* w, 
   g.out = out; g.ldo = ldo; g.out_dtype = PSO_ELEM;
   g.out2 = out_pre; g.ldo2 = ld_pre;
   g.tail_m = (pre_rows > 0 && pre_rows < M) ? pre_rows : M;
-  g.vec_ok = 1; g.rows_per_group = 1;
-  g.group_m = g_gemm_group > 0 ? g_gemm_group : PSO_GEMM_GROUP_M;
-  // the 8-phase kernel with the LDS-staged epilogue (gemm8p.hip): 16384 x 10240 x 1280 1023 vs 801 TF/s,
-  // 65536 x 5120 x 640 814 vs 640 (tools/gemm_bench.py, one box), inside the C2 step 1006 vs 922 / 801 vs 706
-  // (tools/shape_prof.py); variant 31 keeps the 2-phase 256x256 kernel
-  // 256 x 320 tiles where they cost fewer tile-rounds than 256 x 256 (rounds x tile width: bs = 1's 4096 x 10240:
-  // 2 x 320 < 3 x 256; C3's 6144 x 10240: 3 x 320 < 4 x 256; C5's 2048 x 10240: 1 x 320 < 2 x 256; equal at C2's
-  // whole-round shapes, which keep 256 x 256); same bits either way.  Variant 57 keeps 256 x 256.
-  if (g_gemm_variant != 31 && g_gemm_variant != 57 && (K % 64) == 0 && (N % 320) == 0 && lda == ldw &&
-      fits30(M, lda) && fits30(N, ldw)) {
-    const long r256 = ((long)((M + 255) / 256) * (N / 256) + 255) / 256, r320 = ((long)((M + 255) / 256) * (N / 320) + 255) / 256;
-    // variant 58 (knob): 256 x 320 at equal rounds too (C2's shapes)
-    if (r320 * 320 < r256 * 256 || (g_gemm_variant == 58 && r320 * 320 == r256 * 256))
-      return pso_gemm8p320_geglu_run(M, N, K, a, lda, w, ldw, bias, out, ldo, out_pre, ld_pre, g.tail_m, g.group_m,
-                                     (hipStream_t)stream);
-  }
-  if (g_gemm_variant != 31 && (K % 64) == 0 && fits30(M, lda) && fits30(N, ldw))
-    return pso_gemm8p_run(1, M, N, K, a, lda, w, ldw, nullptr, 0, 0, nullptr, 0, 0, 0, 1.f, bias, nullptr, 0, out, ldo,
-                          out_pre, ld_pre, g.tail_m, nullptr, 0, g.group_m, (hipStream_t)stream);
-#ifdef PSO_BENCH_KNOBS  // tile A/B knobs (64-column wave tiles are what the interleaved epilogue needs)
-  if (g_gemm_variant == 33) return launch<128, 128, 2, 2, 2, false, EPI_GEGLU>(g, (hipStream_t)stream);
-  if (g_gemm_variant == 34) return launch<128, 256, 2, 4, 2, false, EPI_GEGLU>(g, (hipStream_t)stream);
-  if (g_gemm_variant == 35) return launch<256, 128, 4, 2, 2, false, EPI_GEGLU>(g, (hipStream_t)stream);
-  if (g_gemm_variant == 36) return launch<128, 128, 2, 2, 3, false, EPI_GEGLU>(g, (hipStream_t)stream);
-#endif
-  return launch<256, 256, 2, 4, 2, false, EPI_GEGLU>(g, (hipStream_t)stream);
+  g.rows_per_group = 1;
+  return run_plan(geglu_plan(M, N, K, lda == ldw, fits30(M, lda) && fits30(N, ldw), g_gemm_knobs), g,
+                  (hipStream_t)stream);
 }
 
 int pso_gemm_geglu_bwd(int M, int N, const void* a, long lda, int K, const void* w, long ldw, const void* pre,
@@ -1888,31 +1566,84 @@ int pso_gemm_geglu_bwd(int M, int N, const void* a, long lda, int K, const void*
   g.M = M; g.N = N; g.alpha = 1.f;
   g.out = out; g.ldo = ldo; g.out_dtype = PSO_ELEM;
   g.aux = (const bf16_t*)pre; g.ldaux = ld_pre;
-  g.vec_ok = 1; g.rows_per_group = 1;
-  g.group_m = g_gemm_group > 0 ? g_gemm_group : PSO_GEMM_GROUP_M;
-  const hipStream_t st = (hipStream_t)stream;
-  // 256 x 320 tiles where they make whole rounds the 256 x 256 ones do not (8192 x 5120: 512 tiles = 2 rounds vs 640 =
-  // 2.5; 32768 x 2560: 1024 = 4 vs 1280 = 5); variant 45 keeps the 256 x 256 form
-  if (g_gemm_variant != 45 && g_gemm_variant != 31 && (N % 320) == 0 && (K % 64) == 0 && lda == ldw && fits30(M, lda) &&
-      fits30(N, ldw) && ((long)((M + 255) / 256) * (N / 320)) % 256 == 0)
-    return pso_gemm8p320_geglu_bwd_run(M, N, K, a, lda, w, ldw, pre, ld_pre, out, ldo, g.group_m, st);
-  // 8-phase form (staggered wave groups) by default: 716 vs 658 TF/s for the 2-phase 128x160 kernel at
-  // 16384 x 5120 x 1280, 489 vs 472 at 65536 x 2560 x 640 (tools/gemm_bench.py, one box); variant 31 keeps 128x160
-  // (from two rounds of tiles: below that the 2-phase 128 x 160 tiles with two workgroups per CU win -- bs = 1's
-  // 2048 x 5120 x 1280 620 vs 493-522 TF/s, C3's 6144 x 5120 x 1280 719 vs 680; tools/small_m_bench.py GEGLU_BWD=1)
-  if (g_gemm_variant != 31 && (N % 256) == 0 && (K % 64) == 0 && fits30(M, lda) &&
-      fits30(N, ldw) && (long)((M + 255) / 256) * (N / 256) >= 512)
-    return pso_gemm8p_run(2, M, N, K, a, lda, w, ldw, nullptr, 0, 0, nullptr, 0, 0, 0, 1.f, nullptr, nullptr, 0, out,
-                          ldo, nullptr, 0, 0, pre, ld_pre, g.group_m, st);
-  const long t160 = (long)((M + 127) / 128) * ((N + 159) / 160);
-  if ((N % 160) == 0 && t160 >= 256) return launch<128, 160, 2, 2, 2, false, EPI_GEGLU_BWD>(g, st);
-  return launch<64, 64, 2, 2, 2, false, EPI_GEGLU_BWD>(g, st);
+  g.rows_per_group = 1;
+  return run_plan(geglu_bwd_plan(M, N, K, lda == ldw, fits30(M, lda) && fits30(N, ldw), g_gemm_knobs), g,
+                  (hipStream_t)stream);
 }
 
 #ifdef PSO_BENCH_KNOBS
 void pso_gemm_set_variant(int v) {
-  g_gemm_variant = v % 100;
-  g_gemm_group = v / 100;
+  g_gemm_knobs.variant = v % 100;
+  g_gemm_knobs.group = v / 100;
+}
+void pso_gemm_tn_set_split(int ks) { g_gemm_knobs.tn_split = ks; }
+
+static const void* plan_query_ptr(int align) { return align > 0 ? (const void*)(uintptr_t)(0x10000 + (align & 15)) : nullptr; }
+
+// gemm_plan.h's answer for a problem given by value (include/pso_amd_knobs.h): the entries' own argument checks and
+// fillers run on stand-in addresses of the given alignment, which are never dereferenced; nothing is launched
+int pso_gemm_plan_query(int kind, const PsoGemmPlanQuery* q, PsoGemmPlanInfo* info) {
+  PSO_ARG_CHECK(q && info, "pso_gemm_plan_query: null argument");
+  GemmKnobs k;
+  k.variant = q->variant; k.group = q->group; k.tn_split = q->tn_split;
+  const void* const op = plan_query_ptr(16);
+  void* const out = (void*)plan_query_ptr(q->out_align);
+  const void *bias = plan_query_ptr(q->bias_align), *rowbias = plan_query_ptr(q->rowbias_align),
+             *resid = plan_query_ptr(q->resid_align), *tail = q->K2 > 0 ? op : nullptr;
+  *info = PsoGemmPlanInfo{};
+  GemmPlan p;
+  GemmArgs g{};
+  bool small_conv_entry = false;
+  switch (kind) {
+    case PSO_PLAN_GEMM: {
+      const int rc = gemm_entry_args("pso_gemm_plan_query", g, q->M, q->N, op, q->lda1, q->K1, op, q->ldb1, tail,
+                                     q->lda2, q->K2, tail, q->ldb2, q->alpha, bias, rowbias, q->ld_rowbias,
+                                     q->rows_per_group, resid, q->ldr, out, q->ldo, q->out_dtype, q->accumulate,
+                                     q->tail_group_n, q->tail_rows);
+      if (rc != PSO_OK) return rc;
+      break;
+    }
+    case PSO_PLAN_CONV: {
+      const int rc = conv_entry_args("pso_gemm_plan_query", g, q->conv_mode, q->B, op, q->C1, q->C2 ? op : nullptr,
+                                     q->C2, q->H, q->W, q->Ho, q->Wo, q->ks, q->stride, q->pad, op, q->N, tail, q->lda2,
+                                     q->K2, tail, q->ldb2, q->alpha, bias, rowbias, q->ld_rowbias, resid, q->ldr, out,
+                                     q->ldo, q->out_dtype, q->accumulate);
+      if (rc != PSO_OK) return rc;
+      small_conv_entry = !q->have_ws && q->alpha == 1.f && q->ldo == q->N;
+      break;
+    }
+    case PSO_PLAN_BATCHED:
+      g = batched_args(q->batch, q->M, q->N, q->K1, op, q->lda1, 0, op, q->ldb1, 0, q->alpha, out, q->ldo, 0,
+                       q->out_dtype);
+      break;
+    case PSO_PLAN_GEGLU:
+    case PSO_PLAN_GEGLU_BWD: {
+      const bool fits = fits30(q->M, q->lda1) && fits30(q->N, q->ldb1);
+      p = kind == PSO_PLAN_GEGLU ? geglu_plan(q->M, q->N, q->K1, q->lda1 == q->ldb1, fits, k)
+                                 : geglu_bwd_plan(q->M, q->N, q->K1, q->lda1 == q->ldb1, fits, k);
+      break;
+    }
+    case PSO_PLAN_TN:
+    case PSO_PLAN_TN_GEGLU: {
+      const TnPlan t = kind == PSO_PLAN_TN_GEGLU
+                           ? tn_geglu_plan(q->M, q->N, q->K1, q->lda1, q->ldb1, k)
+                           : tn_plan(q->M, q->N, q->K1, q->lda1, q->ldb1, q->tn_group, q->have_ws != 0, k);
+      info->form = t.kind;
+      info->ws_ks = t.ws ? t.ks : 0;
+      info->atomic_ks = t.ws ? 1 : t.ks;
+      return PSO_OK;
+    }
+    default: PSO_ARG_CHECK(false, "pso_gemm_plan_query: bad kind %d", kind);
+  }
+  if (kind <= PSO_PLAN_BATCHED) {
+    g.ws = q->have_ws ? (float*)op : nullptr;
+    p = gemm_plan(gemm_facts(g, q->have_ws ? ~(size_t)0 : 0, small_conv_entry), k);
+  }
+  info->form = p.form; info->bm = p.BM; info->bn = p.BN; info->wm = p.WM; info->wn = p.WN; info->stages = p.STAGES;
+  info->pipe = p.PIPE; info->epi = p.epi; info->conv_mode = p.form == GF_TILE && p.epi == GEPI_NONE ? g.conv.mode : 0;
+  info->atomic_ks = p.atomic_ks; info->ws_ks = p.ws_ks;
+  info->stage_epi = p.stage_epi; info->vec_ok = p.vec_ok; info->group_m = p.group_m;
+  return PSO_OK;
 }
 #endif
 
@@ -1929,9 +1660,6 @@ int pso_gemm_tn(int M, int I, int J, const void* A, long lda, const void* B, lon
                 long ldo, void* stream) {
   return pso_gemm_tn_grouped(M, I, J, A, lda, B, ldb, alpha, out, ldo, 0, stream);
 }
-#ifdef PSO_BENCH_KNOBS
-void pso_gemm_tn_set_split(int ks) { g_tn_split = ks; }
-#endif
 
 int pso_gemm_tn_grouped(int M, int I, int J, const void* A, long lda, const void* B, long ldb, float alpha, float* out,
                         long ldo, int group, void* stream) {
@@ -1939,61 +1667,12 @@ int pso_gemm_tn_grouped(int M, int I, int J, const void* A, long lda, const void
   PSO_ARG_CHECK(al16(A) && al16(B) && (lda % 8) == 0 && (ldb % 8) == 0 && (I % 8) == 0 && (J % 8) == 0,
                 "pso_gemm_tn: operands need 16-B aligned rows and I, J multiples of 8");
   if (M == 0) return PSO_OK;
-  // One side a rank-r projection (LoRA): the streaming rank kernel.  group > 0 (block-diagonal fused q/k/v): the big
-  // side's column c pairs with the small side's columns [(c / group) * r, +r) where r = small width / (big / group).
-  auto rk = [](int r) { return r == 16 || r == 32 || r == 64 || r == 96; };
-  if (g_tn_split == 0) {
-    if (I % 128 == 0 && (group == 0 ? rk(J) : (group % 128 == 0 && I % group == 0 && rk(J / (I / group)))))
-      return pso_gemm_tn_rank(M, I, A, lda, B, ldb, group ? J / (I / group) : J, group, alpha, out, ldo, 0,
-                              (hipStream_t)stream);
-    if (J % 128 == 0 && group == 0 && rk(I))
-      return pso_gemm_tn_rank(M, J, B, ldb, A, lda, I, 0, alpha, out, ldo, 1, (hipStream_t)stream);
-  }
-  PSO_ARG_CHECK(group == 0, "pso_gemm_tn: grouped form needs a rank-32/64/96 side and 128 | group");
-  const int nkt = (M + 63) / 64;
-  if (g_tn_split == 0 && tn256_slices(M, I, J, lda, ldb) == 1) {
-    tn256_launch(M, I, J, A, lda, B, ldb, alpha, out, ldo, 1, nullptr, 0, (hipStream_t)stream);
-    return pso_check_launch("pso_gemm_tn");
-  }
-  // full-weight gradients (both sides >= 128 wide): 128 x 128 tiles; split over M only as far as needed to cover ~2
-  // rounds of co-resident blocks (each split adds its tile of f32 atomics)
-#ifdef PSO_BENCH_KNOBS
-  static const int tn128 = [] {
-    const char* e = getenv("PSO_TN128");  // benchmark knob: 0 keeps the 64 x 64 kernel everywhere
-    return e ? atoi(e) : 1;
-  }();
-#else
-  constexpr int tn128 = 1;
-#endif
-  const int t128 = ((I + 127) / 128) * ((J + 127) / 128);
-  if (tn128 && g_tn_split == 0 && I >= 128 && J >= 128 && (long)M * lda < (1L << 30) && (long)M * ldb < (1L << 30)) {
-    // split over M only while its f32 atomics stay small next to the product: each split adds I*J*4 bytes at the
-    // ~1.3 TB/s atomic rate against 2*M*I*J flop, so ks <= M / 16384 keeps them under ~10 %
-    int ks = (512 + t128 - 1) / t128;
-    if (ks > M / 16384) ks = M / 16384;
-    if (ks < 1) ks = 1;
-    const int steps = (nkt + ks - 1) / ks;
-    ks = (nkt + steps - 1) / steps;
-  // fewer than 128 blocks (e.g. 640 x 640 weights: 25 tiles) leave most CUs idle: the 64 x 64 kernel's 4x the tiles
-  // win there (C3 step shape_prof: 24576 x 640 x 640 122 vs 59 TF/s, 6144 x 1280 x 1280 234 vs 213; the 128 x 128
-  // tiles elsewhere: 6144 x 10240 x 1280 697 vs 417, 98304 x 320 x 2880 485 vs 141, 6144 x 1280 x 11520 815 vs 431)
-  if (t128 * ks >= 128) {
-    pso_note_kernel("gemm_tn128_kernel");
-    gemm_tn128_kernel<<<dim3(t128, ks), 256, 0, (hipStream_t)stream>>>(M, I, J, (const bf16_t*)A, lda,
-                                                                        (const bf16_t*)B, ldb, alpha, out, ldo, steps,
-                                                                        nullptr);
-    return pso_check_launch("pso_gemm_tn");
-  }
-  }
-  const int tiles = ((I + 63) / 64) * ((J + 63) / 64);
-  // ~160 blocks: fewer leaves the M-range latency-bound, more multiplies the f32 atomics (measured optimum on the
-  // LoRA dW shapes, M = 4096 / 16384, I x J = 1280x32 .. 640x32)
-  int ks = g_tn_split > 0 ? g_tn_split : (160 + tiles - 1) / tiles;
-  if (ks > nkt) ks = nkt;
-  if (ks < 1) ks = 1;
-  pso_note_kernel("gemm_tn_kernel");
-  gemm_tn_kernel<<<dim3(tiles, ks), 256, 0, (hipStream_t)stream>>>(M, I, J, (const bf16_t*)A, lda, (const bf16_t*)B,
-                                                                   ldb, alpha, out, ldo, nullptr);
+  const TnPlan p = tn_plan(M, I, J, lda, ldb, group, false, g_gemm_knobs);
+  if (p.kind == TNP_RANK)
+    return p.swap ? pso_gemm_tn_rank(M, J, B, ldb, A, lda, p.rank, 0, alpha, out, ldo, 1, (hipStream_t)stream)
+                  : pso_gemm_tn_rank(M, I, A, lda, B, ldb, p.rank, group, alpha, out, ldo, 0, (hipStream_t)stream);
+  PSO_ARG_CHECK(p.kind != TNP_BAD_GROUP, "pso_gemm_tn: grouped form needs a rank-32/64/96 side and 128 | group");
+  tn_launch_tiles(p, M, I, J, A, lda, B, ldb, alpha, out, ldo, nullptr, (hipStream_t)stream);
   return pso_check_launch("pso_gemm_tn");
 }
 
@@ -2004,16 +1683,15 @@ int pso_gemm_tn_geglu(int M, int F2, int J, const void* A, long lda, const void*
   PSO_ARG_CHECK(al16(A) && al16(B) && (lda % 8) == 0 && (ldb % 8) == 0, "pso_gemm_tn_geglu: 16-B aligned rows");
   PSO_ARG_CHECK((long)M * lda < (1L << 30) && (long)M * ldb < (1L << 30), "pso_gemm_tn_geglu: operand too large");
   if (M == 0) return PSO_OK;
-  // one pass over the reduction rows (no split: += straight into the natural-order gradient, deterministic)
-  if (tn256_slices(M, F2, J, lda, ldb) == 1) {
+  const TnPlan p = tn_geglu_plan(M, F2, J, lda, ldb, g_gemm_knobs);
+  if (p.kind == TNP_256) {
     tn256_launch(M, F2, J, A, lda, B, ldb, alpha, out, ldo, 1, nullptr, F2 / 2, (hipStream_t)stream);
     return pso_check_launch("pso_gemm_tn_geglu");
   }
   const int t128 = (F2 / 128) * ((J + 127) / 128);
   pso_note_kernel("gemm_tn128_kernel");
   gemm_tn128_kernel<<<dim3(t128, 1), 256, 0, (hipStream_t)stream>>>(M, F2, J, (const bf16_t*)A, lda, (const bf16_t*)B,
-                                                                     ldb, alpha, out, ldo, (M + 63) / 64, nullptr,
-                                                                     F2 / 2);
+                                                                     ldb, alpha, out, ldo, p.steps, nullptr, F2 / 2);
   return pso_check_launch("pso_gemm_tn_geglu");
 }
 

@@ -31,7 +31,7 @@
 // fragment is 32 consecutive k (two ds_read_b128) and one v_mfma_scale_f32_16x16x128_f8f6f4 per 16 x 16 subtile
 // applies the row and column scales in the MFMA (per-lane scale bytes, op_sel picks the subtile's byte), so the
 // accumulator is in true units and the epilogues are the bf16 form's.
-#include "common.h"
+#include "gemm_args.h"
 
 #include <cstdlib>
 
@@ -40,29 +40,6 @@
 #define EPI8_GEGLU_BWD 2
 
 typedef __attribute__((address_space(3))) void lds8_void;
-
-struct Gemm8Args {
-  const bf16_t* a; long lda;
-  const bf16_t* w; long ldw;
-  int M, N, K;
-  const bf16_t* a2; long lda2; int K2;  // LoRA K-tail (a2 null: none); a2 has tail_m rows
-  const bf16_t* w2; long ldw2;
-  int tail_m, tail_group_n;              // tail_group_n > 0: column group j takes a2 columns [j*K2, (j+1)*K2)
-  float alpha;
-  const bf16_t* bias;
-  const bf16_t* resid; long ldr;
-  void* out; long ldo;
-  void* out2; long ldo2; int pre_rows;  // EPI_GEGLU: interleaved pre-activation of rows < pre_rows (optional)
-  const bf16_t* aux; long ldaux;        // EPI_GEGLU_BWD: interleaved pre-activation [M][2N]
-  int group_m;
-  int skip_epi;  // benchmark knob: accumulators kept live, nothing stored (main-loop time alone)
-  // FP8 form: E8M0 scale bytes of the rows of A (M), of W (N), of A2 (tail_m) and of W2 (N)
-  const uint8_t* sa; const uint8_t* sw; const uint8_t* sa2; const uint8_t* sw2;
-  // CONV form (3x3, stride 1, pad 1, NHWC, A = the [B*H*W][C] image with lda = C): image height / width, K-tiles per
-  // tap (C / 64) and its 2^20-scaled reciprocal; per-image row bias rowbias[m / (H*W)][N] (the time embedding)
-  int cv_H, cv_W, cv_lh, cv_lw, cv_ct, cv_recip;  // H, W powers of two (lh / lw their logs), W >= 8
-  const bf16_t* rowbias; long ld_rowbias;
-};
 
 int pso_gemm_group_knob();  // gemm.hip: the raster-group benchmark knob (0 = automatic)
 
@@ -954,8 +931,7 @@ int launch8s(const Gemm8Args& g, hipStream_t st, int mode) {
 
 }  // namespace
 
-// Host entries used by gemm.hip (preconditions checked there): N % 256 == 0, K % 64 == 0, 16-B aligned rows, every
-// operand's M * ld (or N * ld) below 2^30 elements (byte offsets of the buffer loads are 32-bit).
+// Host entry used by gemm.hip (gemm_args.h; preconditions checked by gemm_plan.h)
 #ifdef PSO_BENCH_KNOBS
 static int g_skip_epi8 = 0;
 // benchmark knobs, bit 1: wave groups in lockstep (default: staggered by half a phase, +10-18 % on every UNet shape,
@@ -966,91 +942,22 @@ extern "C" void pso_gemm8p_skip_epilogue(int on) { g_skip_epi8 = on & 1; g_mode8
 static constexpr int g_skip_epi8 = 0, g_mode8 = 0;
 #endif
 
-int pso_gemm8p_run(int epi, int M, int N, int K, const void* a, long lda, const void* w, long ldw, const void* a2,
-                   long lda2, int K2, const void* w2, long ldw2, int tail_m, int tail_group_n, float alpha,
-                   const void* bias, const void* resid, long ldr, void* out, long ldo, void* out2, long ldo2,
-                   int pre_rows, const void* aux, long ldaux, int group_m, hipStream_t st) {
-  Gemm8Args g{};
-  g.a = (const bf16_t*)a; g.lda = lda; g.w = (const bf16_t*)w; g.ldw = ldw;
-  g.M = M; g.N = N; g.K = K;
-  g.a2 = (const bf16_t*)a2; g.lda2 = lda2; g.K2 = a2 ? K2 : 0; g.w2 = (const bf16_t*)w2; g.ldw2 = ldw2;
-  g.tail_m = tail_m; g.tail_group_n = a2 ? tail_group_n : 0;
-  g.alpha = alpha; g.bias = (const bf16_t*)bias; g.resid = (const bf16_t*)resid; g.ldr = ldr;
-  g.out = out; g.ldo = ldo; g.out2 = out2; g.ldo2 = ldo2; g.pre_rows = pre_rows;
-  g.aux = (const bf16_t*)aux; g.ldaux = ldaux;
-  g.group_m = group_m; g.skip_epi = g_skip_epi8;
+int pso_gemm8p_launch(int bn, int epi, bool conv, Gemm8Args g, hipStream_t st) {
+  g.skip_epi = g_skip_epi8;
+  if (conv) {  // 3x3 / stride 1 / pad 1 on 256 x 320 tiles: weight rows [Cout][3][3][C], C = lda, bf16 output
+    g.cv_lh = __builtin_ctz(g.cv_H); g.cv_lw = __builtin_ctz(g.cv_W);
+    g.cv_ct = (int)g.lda / 64; g.cv_recip = (1 << 20) / g.cv_ct + 1;
+    return launch8<EPI8_NONE, true, false, false, 320, true>(g, st);
+  }
+  if (bn == 160) return launch8<EPI8_NONE, true, false, false, 160>(g, st);
+  if (bn == 320) {  // lda == ldw; the GEGLU forms are bit-identical to the 256 x 256 ones
+    if (epi == EPI8_GEGLU) return launch8<EPI8_GEGLU, true, false, false, 320>(g, st);
+    if (epi == EPI8_GEGLU_BWD) return launch8<EPI8_GEGLU_BWD, true, false, false, 320>(g, st);
+    return launch8<EPI8_NONE, true, false, false, 320>(g, st);
+  }
   if (epi == EPI8_GEGLU) return launch8s<EPI8_GEGLU>(g, st, g_mode8);
   if (epi == EPI8_GEGLU_BWD) return launch8s<EPI8_GEGLU_BWD>(g, st, g_mode8);
   return launch8s<EPI8_NONE>(g, st, g_mode8);
-}
-
-// 256 x 160 tiles (N % 160 == 0, K % 64 == 0, plain epilogue; preconditions checked in gemm.hip)
-int pso_gemm8p160_run(int M, int N, int K, const void* a, long lda, const void* w, long ldw, const void* a2, long lda2,
-                      int K2, const void* w2, long ldw2, int tail_m, int tail_group_n, float alpha, const void* bias,
-                      const void* resid, long ldr, void* out, long ldo, int group_m, hipStream_t st) {
-  Gemm8Args g{};
-  g.a = (const bf16_t*)a; g.lda = lda; g.w = (const bf16_t*)w; g.ldw = ldw;
-  g.M = M; g.N = N; g.K = K;
-  g.a2 = (const bf16_t*)a2; g.lda2 = lda2; g.K2 = a2 ? K2 : 0; g.w2 = (const bf16_t*)w2; g.ldw2 = ldw2;
-  g.tail_m = tail_m; g.tail_group_n = a2 ? tail_group_n : 0;
-  g.alpha = alpha; g.bias = (const bf16_t*)bias; g.resid = (const bf16_t*)resid; g.ldr = ldr;
-  g.out = out; g.ldo = ldo; g.group_m = group_m; g.skip_epi = g_skip_epi8;
-  return launch8<EPI8_NONE, true, false, false, 160>(g, st);
-}
-
-// 256 x 320 tiles (N % 320 == 0, K % 64 == 0, plain epilogue; preconditions checked in gemm.hip)
-int pso_gemm8p320_run(int M, int N, int K, const void* a, long lda, const void* w, long ldw, const void* a2, long lda2,
-                      int K2, const void* w2, long ldw2, int tail_m, int tail_group_n, float alpha, const void* bias,
-                      const void* resid, long ldr, void* out, long ldo, int group_m, hipStream_t st) {
-  Gemm8Args g{};
-  g.a = (const bf16_t*)a; g.lda = lda; g.w = (const bf16_t*)w; g.ldw = ldw;
-  g.M = M; g.N = N; g.K = K;
-  g.a2 = (const bf16_t*)a2; g.lda2 = lda2; g.K2 = a2 ? K2 : 0; g.w2 = (const bf16_t*)w2; g.ldw2 = ldw2;
-  g.tail_m = tail_m; g.tail_group_n = a2 ? tail_group_n : 0;
-  g.alpha = alpha; g.bias = (const bf16_t*)bias; g.resid = (const bf16_t*)resid; g.ldr = ldr;
-  g.out = out; g.ldo = ldo; g.group_m = group_m; g.skip_epi = g_skip_epi8;
-  return launch8<EPI8_NONE, true, false, false, 320>(g, st);
-}
-
-// GEGLU forward on 256 x 320 tiles (N % 320 == 0, lda == ldw; preconditions checked in gemm.hip): the interleaved
-// pre-activation a . w^T + bias (rows < pre_rows to out2) and out = h * gelu(gate), bit-identical to the 256 x 256 form
-int pso_gemm8p320_geglu_run(int M, int N, int K, const void* a, long lda, const void* w, long ldw, const void* bias,
-                            void* out, long ldo, void* out2, long ldo2, int pre_rows, int group_m, hipStream_t st) {
-  Gemm8Args g{};
-  g.a = (const bf16_t*)a; g.lda = lda; g.w = (const bf16_t*)w; g.ldw = ldw;
-  g.M = M; g.N = N; g.K = K; g.tail_m = M;
-  g.alpha = 1.f; g.bias = (const bf16_t*)bias;
-  g.out = out; g.ldo = ldo; g.out2 = out2; g.ldo2 = ldo2; g.pre_rows = pre_rows;
-  g.group_m = group_m; g.skip_epi = g_skip_epi8;
-  return launch8<EPI8_GEGLU, true, false, false, 320>(g, st);
-}
-
-// GEGLU backward on 256 x 320 tiles (N % 320 == 0, lda == ldw; preconditions checked in gemm.hip): dout = a . w^T,
-// out = the interleaved [dout * gelu(g) | dout * h * gelu'(g)] from the interleaved pre-activation aux
-int pso_gemm8p320_geglu_bwd_run(int M, int N, int K, const void* a, long lda, const void* w, long ldw, const void* aux,
-                                long ldaux, void* out, long ldo, int group_m, hipStream_t st) {
-  Gemm8Args g{};
-  g.a = (const bf16_t*)a; g.lda = lda; g.w = (const bf16_t*)w; g.ldw = ldw;
-  g.M = M; g.N = N; g.K = K; g.tail_m = M;
-  g.alpha = 1.f; g.out = out; g.ldo = ldo; g.aux = (const bf16_t*)aux; g.ldaux = ldaux;
-  g.group_m = group_m; g.skip_epi = g_skip_epi8;
-  return launch8<EPI8_GEGLU_BWD, true, false, false, 320>(g, st);
-}
-
-// 3x3 / stride 1 / pad 1 implicit-GEMM convolution on 256 x 320 tiles (preconditions checked in gemm.hip: C % 64 == 0,
-// H*W % 256 == 0, Cout % 320 == 0, weight rows [Cout][3][3][C], bf16 output)
-int pso_gemm8p320_conv_run(int B, int H, int W, int C, const void* x, const void* w, int Cout, float alpha,
-                           const void* bias, const void* rowbias, long ld_rowbias, const void* resid, long ldr,
-                           void* out, long ldo, int group_m, hipStream_t st) {
-  Gemm8Args g{};
-  g.a = (const bf16_t*)x; g.lda = C; g.w = (const bf16_t*)w; g.ldw = 9L * C;
-  g.M = B * H * W; g.N = Cout; g.K = 9 * C;
-  g.tail_m = g.M;
-  g.alpha = alpha; g.bias = (const bf16_t*)bias; g.resid = (const bf16_t*)resid; g.ldr = ldr;
-  g.out = out; g.ldo = ldo; g.group_m = group_m; g.skip_epi = g_skip_epi8;
-  g.cv_H = H; g.cv_W = W; g.cv_lh = __builtin_ctz(H); g.cv_lw = __builtin_ctz(W); g.cv_ct = C / 64; g.cv_recip = (1 << 20) / (C / 64) + 1;
-  g.rowbias = (const bf16_t*)rowbias; g.ld_rowbias = ld_rowbias;
-  return launch8<EPI8_NONE, true, false, false, 320, true>(g, st);
 }
 
 // FP8 form (pso_amd.h, pso_gemm_fp8): staggered wave groups, epilogue 0 (bias / alpha / residual) or 1 (GEGLU)
@@ -1074,14 +981,14 @@ extern "C" int pso_gemm_fp8(int epi, int M, int N, int K, const void* a, long ld
   PSO_ARG_CHECK(!resid || (a16(resid) && (ldr % 8) == 0), "pso_gemm_fp8: residual needs 16-B aligned rows");
   PSO_ARG_CHECK(epi != EPI8_GEGLU || (bias && !resid && (!out_pre || (a16(out_pre) && (ld_pre % 8) == 0))),
                 "pso_gemm_fp8: GEGLU needs a bias, no residual, aligned out_pre");
-  Gemm8Args g{};
-  g.a = (const bf16_t*)a; g.lda = lda; g.w = (const bf16_t*)w; g.ldw = ldw;
-  g.M = M; g.N = N; g.K = K;
-  g.a2 = (const bf16_t*)a2; g.lda2 = lda2; g.K2 = a2 ? K2 : 0; g.w2 = (const bf16_t*)w2; g.ldw2 = ldw2;
-  g.tail_m = a2 ? (tail_m < M ? tail_m : M) : M; g.tail_group_n = a2 ? tail_group_n : 0;
-  g.alpha = alpha; g.bias = (const bf16_t*)bias; g.resid = (const bf16_t*)resid; g.ldr = ldr;
-  g.out = out; g.ldo = ldo; g.out2 = out_pre; g.ldo2 = ld_pre; g.pre_rows = pre_rows > 0 ? pre_rows : M;
-  g.group_m = 4; g.skip_epi = g_skip_epi8;
+  GemmArgs d{};
+  d.a1 = (const bf16_t*)a; d.lda1 = lda; d.K1 = K; d.b1 = (const bf16_t*)w; d.ldb1 = ldw;
+  d.a2 = (const bf16_t*)a2; d.lda2 = lda2; d.K2 = K2; d.b2 = (const bf16_t*)w2; d.ldb2 = ldw2;
+  d.M = M; d.N = N; d.tail_m = a2 ? (tail_m < M ? tail_m : M) : M; d.tail_group_n = tail_group_n;
+  d.alpha = alpha; d.bias = (const bf16_t*)bias; d.resid = (const bf16_t*)resid; d.ldr = ldr;
+  d.out = out; d.ldo = ldo; d.out2 = out_pre; d.ldo2 = ld_pre; d.group_m = 4;
+  Gemm8Args g = gemm8_args(d);
+  g.pre_rows = pre_rows > 0 ? pre_rows : M; g.skip_epi = g_skip_epi8;
   g.sa = (const uint8_t*)sa; g.sw = (const uint8_t*)sw; g.sa2 = (const uint8_t*)sa2; g.sw2 = (const uint8_t*)sw2;
   const hipStream_t st = (hipStream_t)stream;
   if (epi == EPI8_GEGLU) return launch8<EPI8_GEGLU, true, false, true>(g, st);

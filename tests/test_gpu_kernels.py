@@ -601,6 +601,56 @@ def test_conv_8phase_256x320(cuda, variant, B, C, H, W, Cout):
 
 
 @pytest.mark.knobs
+@pytest.mark.parametrize("variant,entry,shape,kernel", [
+    (0, "pso_gemm", (64, 64, 64), "gemm_bf16_kernel<64, 64, 0, 2, 2, 2, false, 0>"),
+    (0, "pso_gemm", (256, 32, 64), "gemm_skinny_nt_kernel<"),
+    (0, "pso_gemm_ws", (128, 128, 2048), "gemm_bf16_kernel<128, 128, 0, 2, 4, 2, false, 0>"),
+    (30, "pso_gemm", (256, 256, 64), "gemm8p_kernel<0, true, false, false, 256, false>"),
+    (38, "pso_gemm", (256, 160, 64), "gemm8p_kernel<0, true, false, false, 160, false>"),
+    (39, "pso_gemm", (256, 320, 64), "gemm8p_kernel<0, true, false, false, 320, false>"),
+    (44, "pso_conv2d", (1, 16, 64, 320), "gemm8p_kernel<0, true, false, false, 320, true>")])
+def test_launch_is_what_the_plan_says(cuda, variant, entry, shape, kernel):
+    """One real launch per form of csrc/gemm_plan.h at the smallest shape that reaches it: the kernel the entry notes
+    is the one pso_gemm_plan_query plans for the same facts and variant (the query exists in the tools build, so that
+    half runs in the tools-build child; the variant-0 forms are also checked by name in the product-library process),
+    and the result is the fp32 torch product within the bf16-output tolerance of this file's tests of each form."""
+    import ctypes
+    import gemm_plan_cases as C
+    from pairwise_sample_optimization_amd import kernels as K_
+    g = torch.Generator(device="cuda").manual_seed(variant + sum(shape))
+    if variant:
+        K_.gemm_set_variant(variant)
+    try:
+        if entry == "pso_conv2d":
+            B, H, Cin, Cout = shape
+            x = torch.randn(B, Cin, H, H, device=cuda, generator=g).bfloat16()
+            w = (torch.randn(Cout, Cin, 3, 3, device=cuda, generator=g) / (3 * Cin ** 0.5)).bfloat16()
+            out = _nchw(K_.conv2d(_nhwc(x), _nhwc(w)))
+            ref = F.conv2d(x.float(), w.float(), padding=1)
+            case = dict(entry=entry, variant=variant, conv_mode=1, B=B, C1=Cin, H=H, W=H, Ho=H, Wo=H, ks=3, stride=1,
+                        pad=1, N=Cout)
+        else:
+            M, N, K = shape
+            a = torch.randn(M, K, device=cuda, generator=g).bfloat16()
+            w = (torch.randn(N, K, device=cuda, generator=g) / K ** 0.5).bfloat16()
+            assert (K_.lib().pso_gemm_ws_bytes(M, N, K, 0) == 2 * M * N * 4) == (entry == "pso_gemm_ws")  # ks = 2
+            out = K_.gemm(a, w)
+            ref = a.float() @ w.float().t()
+            case = dict(entry=entry, variant=variant, M=M, N=N, K1=K)
+        name = K_.lib().pso_last_kernel().decode()
+    finally:
+        if variant:
+            K_.gemm_set_variant(0)
+    assert name.startswith(kernel) and (name == kernel or kernel.endswith("<")), name
+    if _lib.KNOBS:
+        q, info = _lib.PsoGemmPlanQuery(**C.full(case)), _lib.PsoGemmPlanInfo()
+        kind = C.KIND[entry]
+        assert K_.lib().pso_gemm_plan_query(kind, ctypes.byref(q), ctypes.byref(info)) == 0
+        assert C.plan_of_info(kind, info) == C.plan_of_kernel(name, 2 if entry == "pso_gemm_ws" else 0)
+    assert _rel(out, ref) < 4e-3
+
+
+@pytest.mark.knobs
 @pytest.mark.parametrize("variant", [0, 1, 3, 4, 6, 7, 8, 10, 11, 12, 14, 16, 17, 18, 19, 41])
 def test_conv_every_variant_large(cuda, variant):
     from pairwise_sample_optimization_amd import kernels as K_
