@@ -517,6 +517,63 @@ int pso_adamw8bit_step_blocks_zero_grad_amp(long n, int nblk, const long* desc, 
                                             float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, float lr,
                                             float beta1, float beta2, float eps, float weight_decay,
                                             const void* amp_state, void* stream);
+/* Prodigy (prodigyopt 1.0's Prodigy.step, one parameter group): the DreamBooth script's --optimizer prodigy, DB:622-673
+ * (its own branch, DB:1479-1510, validates the flags and never builds the optimizer).  Parity with the package is
+ * unpinned (prodigyopt is not available here; tests/prodigy_ref.py restates the arithmetic below).  Per-element state on
+ * the flat fp32 buffer: exp_avg (m), exp_avg_sq (v), s -- all zero at the start -- and p0, a copy of the parameters taken
+ * when the state is created.  The scalars live in `state`, a caller-owned block of PSO_PRODIGY_WORDS four-byte words,
+ * 8-B aligned (the f64 fields span two words), that only pso_prodigy_step writes; nothing is read back to the host and
+ * k, d and dlr never travel as arguments.  The caller initialises the block with a copy from the host: D = D0 = D_MAX =
+ * d0 (1e-6 in prodigyopt), every other word zero.  Word w holds
+ *   PSO_PRODIGY_D            f64  d, the running estimate of the distance to the solution
+ *   PSO_PRODIGY_D0           f64  its initial value
+ *   PSO_PRODIGY_D_MAX        f64  the largest d_hat so far (at least d0)
+ *   PSO_PRODIGY_D_NUMERATOR  f64  beta3-discounted sum of dlr (d / d0) <g, p0 - p>
+ *   PSO_PRODIGY_D_DENOM      f64  sum |s| of the last step
+ *   PSO_PRODIGY_D_HAT        f64  d_coef * numerator / denominator of the last applied step
+ *   PSO_PRODIGY_DLR          f64  d * lr * bias correction of the last step, formed with the d the step started from
+ *   PSO_PRODIGY_K            i32  applied steps
+ *   PSO_PRODIGY_UPDATED      i32  1 when the last step moved the parameters, 0 when its denominator was zero
+ *   PSO_PRODIGY_SKIPPED      i32  steps the loss scaler skipped (FOUND_INF)
+ *   the remaining words are reserved (zero).
+ * One step, g = grad * grad_scale * clip_coef[1] (clip_coef may be NULL):
+ *   bc  = sqrt(1 - beta2^(k+1)) / (1 - beta1^(k+1)) with PSO_PRODIGY_BIAS_CORRECTION, else 1;   dlr = d * lr * bc
+ *   without PSO_PRODIGY_DECOUPLE and weight_decay != 0:  g += weight_decay * p
+ *   pass 1 (the d the step started from):  m = beta1 m + d (1 - beta1) g,  v = beta2 v + d^2 (1 - beta2) g^2,
+ *     s = beta3 s + (d / d0) x g with x = d under PSO_PRODIGY_SAFEGUARD_WARMUP, else dlr;
+ *     num = beta3 D_NUMERATOR + (d / d0) dlr sum g (p0 - p),  den = sum |s|
+ *   den == 0: the step ends here (UPDATED = 0; m, v, s stay as just written, p, d, d_max, numerator and k as they were)
+ *   d_hat = d_coef num / den;  if d == d0: d = max(d, d_hat);  d_max = max(d_max, d_hat);
+ *     d = min(d_max, d * growth_rate);  D_NUMERATOR = num;  k += 1
+ *   pass 2 (the new d, the dlr from above):  with PSO_PRODIGY_DECOUPLE and weight_decay != 0: p -= weight_decay dlr p;
+ *     p -= dlr m / (sqrt(v) + d eps)
+ * The element arithmetic is fp32 in this order without contraction; the sums (fp64 products of the fp32 factors, summed
+ * per workgroup into ws and then in a fixed order by one workgroup, so a step is bit-reproducible) and the scalar
+ * algebra are fp64, and a scalar enters the element arithmetic rounded to fp32 once (d (1 - beta1), d^2 (1 - beta2),
+ * (d / d0) x, dlr, weight_decay dlr, d eps).  Buffers 16-B aligned take 16-B loads, others 4-B ones.
+ * beta3: prodigyopt's default is sqrt(beta2), which the caller passes.  growth_rate may be +inf.
+ * amp_state (may be NULL): the loss-scaler block above.  FOUND_INF set: param, exp_avg, exp_avg_sq, s and the state are
+ * left untouched except SKIPPED += 1; otherwise g = grad * GRAD_MUL * CLIP_COEF and grad_scale / clip_coef are not
+ * read.  PSO_ERR_ARG: n <= 0, a null buffer, ws_bytes < pso_prodigy_ws_bytes(n), lr <= 0, unknown flags. */
+#define PSO_PRODIGY_WORDS 24
+#define PSO_PRODIGY_D 0
+#define PSO_PRODIGY_D0 2
+#define PSO_PRODIGY_D_MAX 4
+#define PSO_PRODIGY_D_NUMERATOR 6
+#define PSO_PRODIGY_D_DENOM 8
+#define PSO_PRODIGY_D_HAT 10
+#define PSO_PRODIGY_DLR 12
+#define PSO_PRODIGY_K 14
+#define PSO_PRODIGY_UPDATED 15
+#define PSO_PRODIGY_SKIPPED 16
+#define PSO_PRODIGY_DECOUPLE 1        /* flags: decoupled (AdamW-style) weight decay, else added to the gradient    */
+#define PSO_PRODIGY_BIAS_CORRECTION 2 /*        Adam's bias correction in dlr                                       */
+#define PSO_PRODIGY_SAFEGUARD_WARMUP 4 /*       s accumulates with d instead of dlr                                 */
+size_t pso_prodigy_ws_bytes(long n);
+int pso_prodigy_step(long n, float* param, const float* grad, const float* p0, float* exp_avg, float* exp_avg_sq,
+                     float* s, void* state, float lr, float beta1, float beta2, float beta3, float eps,
+                     float weight_decay, int flags, float d_coef, float growth_rate, float grad_scale,
+                     const float* clip_coef, const void* amp_state, void* ws, size_t ws_bytes, void* stream);
 int pso_preference(int P, int m, const float* rewards, const int64_t* reward_idx, int mode, float* pref,
                    void* stream);
 

@@ -36,6 +36,11 @@ AMP_WORDS = 16
 (AMP_SCALE, AMP_INV_SCALE, AMP_FOUND_INF, AMP_GROWTH_TRACKER, AMP_STEP, AMP_SKIPPED, AMP_NORM, AMP_CLIP_COEF,
  AMP_GRAD_MUL, AMP_BC1, AMP_BC2_SQRT, AMP_C1, AMP_C2) = range(13)
 AMP_INT_WORDS = (AMP_FOUND_INF, AMP_GROWTH_TRACKER, AMP_STEP, AMP_SKIPPED)
+# words of the Prodigy state block (include/pso_amd.h PSO_PRODIGY_*): the f64 fields span two 4-byte words each
+PRODIGY_WORDS = 24
+PRODIGY_F64 = {"d": 0, "d0": 2, "d_max": 4, "d_numerator": 6, "d_denom": 8, "d_hat": 10, "dlr": 12}
+PRODIGY_I32 = {"k": 14, "updated": 15, "skipped": 16}
+PRODIGY_DECOUPLE, PRODIGY_BIAS_CORRECTION, PRODIGY_SAFEGUARD_WARMUP = 1, 2, 4
 
 _lib = None
 
@@ -155,6 +160,9 @@ SIGNATURES = {
                                            vp]),
     "pso_adamw8bit_step_blocks_zero_grad_amp": (ci, [cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf,
                                                      cf, vp, vp]),
+    "pso_prodigy_ws_bytes": (csz, [cl]),
+    "pso_prodigy_step": (ci, [cl, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, cf, ci, cf, cf, cf, vp, vp, vp, csz,
+                              vp]),
     "pso_zero_f32": (ci, [cl, vp, vp]),
     "pso_preference": (ci, [ci, ci, vp, vp, ci, vp, vp]),
     "pso_nhwc_to_nchw": (ci, [ci, ci, cl, vp, vp, ci, vp]),

@@ -22,13 +22,15 @@ weight dtype (DB:1754-1755) and the VAE stays fp32 (DB:1293); noise, add_noise, 
 preconditioning are fp32 -- what prepare_inputs and db_loss.hip compute.
 """
 
+import warnings
+
 import torch
 
 from . import _lib
 from . import kernels as K
 from .amp import DeviceLossScaler, LossScaler, make_scaler
 from .schedulers import EulerDiscreteScheduler, db_distill_timesteps
-from .trainer import OptStep, lora_optimizer_step, trainable_segments
+from .trainer import OptStep, init_optimizer_state, lora_optimizer_step
 
 
 class DreamBoothPSOTrainer:
@@ -37,11 +39,15 @@ class DreamBoothPSOTrainer:
     def __init__(self, unet, vae, loss_type="pso_db", beta_pso=5.0, neg_defactor=0.1, prior_loss_weight=0.5,
                  distill_train_timesteps=4, learning_rate=2e-4, betas=(0.9, 0.999), adam_weight_decay=1e-4,
                  adam_epsilon=1e-8, max_grad_norm=1.0, gradient_accumulation_steps=4, process_group=None,
-                 loss_scale=None, use_8bit_adam=False):
+                 loss_scale=None, use_8bit_adam=False, optimizer="adamw", prodigy_beta3=None, prodigy_decouple=True,
+                 prodigy_use_bias_correction=False, prodigy_safeguard_warmup=False, prodigy_d0=1e-6,
+                 prodigy_d_coef=1.0, prodigy_growth_rate=float("inf")):
         """Defaults: DB argparse defaults (DB:636-674, 757-777) overridden by the recipe scripts/pso_dog.sh.
         loss_scale: None | float (initial scale) | amp.LossScaler | amp.DeviceLossScaler -- fp16 training under the
         f16 library, which refuses to train without one; the bf16 library takes none.  use_8bit_adam: the script's
-        --use_8bit_adam (DB:630), the blockwise 8-bit AdamW as in PSOTrainer."""
+        --use_8bit_adam (DB:630), the blockwise 8-bit AdamW as in PSOTrainer.  optimizer: "adamw" or "prodigy"
+        (--optimizer, DB:622-627; case-insensitive) with the prodigy_* arguments of PSOTrainer; Prodigy wants a
+        learning_rate around 1.0 and reads betas, adam_weight_decay and adam_epsilon as the diffusers script does."""
         if loss_type not in ("pso", "pso_db"):
             raise ValueError(f"Unknown loss type {loss_type}")  # DB:1929
         self.scaler = make_scaler(loss_scale)
@@ -62,10 +68,11 @@ class DreamBoothPSOTrainer:
         self.pg = process_group
         self.sched = EulerDiscreteScheduler()
         st = unet.lora
-        self.adam8 = K.Adam8State(st.master.numel(), st.master.device, segments=trainable_segments(unet)) \
-            if use_8bit_adam else None
-        self.exp_avg = None if use_8bit_adam else torch.zeros_like(st.master)
-        self.exp_avg_sq = None if use_8bit_adam else torch.zeros_like(st.master)
+        init_optimizer_state(self, unet, optimizer=optimizer, use_8bit_adam=use_8bit_adam,
+                             prodigy_beta3=prodigy_beta3, prodigy_decouple=prodigy_decouple,
+                             prodigy_use_bias_correction=prodigy_use_bias_correction,
+                             prodigy_safeguard_warmup=prodigy_safeguard_warmup, prodigy_d0=prodigy_d0,
+                             prodigy_d_coef=prodigy_d_coef, prodigy_growth_rate=prodigy_growth_rate)
         self.clip_buf = torch.zeros(2, device=st.master.device, dtype=torch.float32)
         self.opt_step = 0
         self.n_micro = 0
@@ -73,10 +80,15 @@ class DreamBoothPSOTrainer:
         self.auto_step = True
 
     @classmethod
-    def from_args(cls, unet, vae, args, process_group=None, loss_scale=None):
+    def from_args(cls, unet, vae, args, process_group=None, loss_scale=None, allow_prodigy=False):
         """Build from the reference script's argparse namespace (DB:parse_args).  Read: loss_type, beta_pso,
         neg_defactor, prior_loss_weight, distill_train_timesteps, learning_rate, adam_beta1 / adam_beta2 /
-        adam_weight_decay / adam_epsilon, max_grad_norm, gradient_accumulation_steps, use_8bit_adam, mixed_precision;
+        adam_weight_decay / adam_epsilon, max_grad_norm, gradient_accumulation_steps, use_8bit_adam, mixed_precision,
+        optimizer ("AdamW" or "prodigy"; any other name warns and becomes AdamW, DB:1479-1484) and, for Prodigy,
+        prodigy_beta3 / prodigy_decouple / prodigy_use_bias_correction / prodigy_safeguard_warmup (DB:641-673), which
+        also warns for a learning_rate <= 0.1 and ignores use_8bit_adam with a warning (DB:1486-1490).  Prodigy
+        trains with allow_prodigy=True only: without it optimizer="prodigy" raises ValueError as it always has, so a
+        caller that relied on the refusal keeps it;
         a field the namespace does not carry counts as the script's default.  Flags that ask for training this
         trainer does not implement raise ValueError naming the flag (unet.check_lora_config's rule) instead of
         training something else.
@@ -86,8 +98,30 @@ class DreamBoothPSOTrainer:
         def get(name, default):
             return getattr(args, name, default)
 
-        if str(get("optimizer", "AdamW")).lower() != "adamw":
-            raise ValueError(f"--optimizer={get('optimizer', None)!r} is not implemented (AdamW only; DB:623-627)")
+        optimizer = str(get("optimizer", "AdamW")).lower()
+        if optimizer not in ("adamw", "prodigy"):  # the script's own fallback, DB:1479-1484
+            warnings.warn(f"Unsupported choice of optimizer: {get('optimizer', None)!r}. Supported optimizers include "
+                          "[adamW, prodigy]. Defaulting to adamW")
+            optimizer = "adamw"
+        use_8bit_adam = bool(get("use_8bit_adam", False))
+        prodigy = {}
+        if optimizer == "prodigy":
+            if not allow_prodigy:
+                raise ValueError("--optimizer='prodigy' trains only on request: pass from_args(..., "
+                                 "allow_prodigy=True).  The reference script builds no optimizer for it (DB:1492-1510), "
+                                 "so a namespace that carries it was never a working run there")
+            if use_8bit_adam:  # DB:1486-1490
+                warnings.warn("use_8bit_adam is ignored when optimizer is not set to 'AdamW'. Optimizer was set to "
+                              "prodigy")
+                use_8bit_adam = False
+            if get("learning_rate", 1e-4) <= 0.1:
+                warnings.warn("Learning rate is too low. When using prodigy, it's generally better to set it around "
+                              "1.0")
+            # the script's defaults, DB:641-673: beta3 None (sqrt(beta2)), the three switches on
+            prodigy = dict(prodigy_beta3=get("prodigy_beta3", None),
+                           prodigy_decouple=bool(get("prodigy_decouple", True)),
+                           prodigy_use_bias_correction=bool(get("prodigy_use_bias_correction", True)),
+                           prodigy_safeguard_warmup=bool(get("prodigy_safeguard_warmup", True)))
         for flag in ("train_text_encoder", "with_prior_preservation", "use_dora"):
             if get(flag, False):
                 raise ValueError(f"--{flag} is not implemented (the recipes under personalization/scripts leave it off)")
@@ -117,7 +151,7 @@ class DreamBoothPSOTrainer:
                    adam_weight_decay=get("adam_weight_decay", 1e-4), adam_epsilon=get("adam_epsilon", 1e-8),
                    max_grad_norm=get("max_grad_norm", 1.0),
                    gradient_accumulation_steps=get("gradient_accumulation_steps", 1), process_group=process_group,
-                   loss_scale=loss_scale, use_8bit_adam=bool(get("use_8bit_adam", False)))
+                   loss_scale=loss_scale, use_8bit_adam=use_8bit_adam, optimizer=optimizer, **prodigy)
 
     @property
     def loss_scale(self):

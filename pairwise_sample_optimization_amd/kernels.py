@@ -5,6 +5,7 @@ are channels-last bf16: linear inputs are [tokens, C] (any 2-D row-strided view)
 There is no CPU / eager fallback: a missing library or a host tensor raises PsoLibError.
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -1111,6 +1112,70 @@ def adamw8bit_step_amp(param, grad, state, lr, betas, eps, weight_decay, amp_sta
                              ptr(state.v32), float(lr), float(betas[0]), float(betas[1]), float(eps),
                              float(weight_decay), ptr(amp_state), stream_ptr()), fn)
     return zero_grad
+
+
+class ProdigyState:
+    """State of the Prodigy optimizer (pso_prodigy_step, include/pso_amd.h PSO_PRODIGY_*) for the flat fp32 buffer
+    `master`: p0 (a copy of the parameters as they are now), the moments m and v, the direction sum s, and the scalar
+    state block on the device -- int32 [PRODIGY_WORDS] words, the f64 fields two words each, initialised here by a
+    host-side fill (d = d0 = d_max = `d0`, everything else zero)."""
+
+    def __init__(self, master, d0=1e-6):
+        if not d0 > 0.0:
+            raise ValueError(f"ProdigyState: d0 must be positive, got {d0!r}")
+        self.p0 = master.detach().clone()
+        self.exp_avg = torch.zeros_like(master)
+        self.exp_avg_sq = torch.zeros_like(master)
+        self.s = torch.zeros_like(master)
+        host = torch.zeros(_lib.PRODIGY_WORDS, dtype=torch.int32)
+        f64 = host.view(torch.float64)
+        for name in ("d", "d0", "d_max"):
+            f64[_lib.PRODIGY_F64[name] // 2] = float(d0)
+        self.state = host.to(master.device)
+        self.ws = None  # the partial-sum workspace, allocated at the first step
+
+    def tensors(self):
+        """The state tensors a checkpoint holds (name -> tensor)."""
+        return {"p0": self.p0, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "s": self.s,
+                "prodigy_state": self.state}
+
+    def scalars(self):
+        """The state block as a dict (d, d0, d_max, d_numerator, d_denom, d_hat, dlr: float; k, updated, skipped:
+        int).  Copies the block to the host -- a sync, for tests, logs and checkpoints only."""
+        host = self.state.cpu()
+        f64 = host.view(torch.float64)
+        out = {name: float(f64[w // 2]) for name, w in _lib.PRODIGY_F64.items()}
+        out.update({name: int(host[w]) for name, w in _lib.PRODIGY_I32.items()})
+        return out
+
+
+def prodigy_step(param, grad, state, lr, betas, eps, weight_decay, beta3=None, decouple=True,
+                 use_bias_correction=False, safeguard_warmup=False, d_coef=1.0, growth_rate=float("inf"),
+                 grad_scale=1.0, clip=None, amp_state=None):
+    """One Prodigy step on the flat fp32 param with state = ProdigyState: three launches, nothing read back (k, d and
+    dlr live in the state block).  beta3 None = sqrt(beta2), prodigyopt's default.  amp_state: an
+    amp.DeviceLossScaler's state -- the gradient factor and the inf-skip come from it and grad_scale / clip are not
+    read."""
+    require_cuda(param, grad)
+    if amp_state is not None:
+        _check_amp_state(amp_state)
+    n = param.numel()
+    for t in (grad, state.p0, state.exp_avg, state.exp_avg_sq, state.s):
+        if t.numel() != n or t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.PsoLibError("prodigy_step: grad and the state need param's size, float32 and contiguous")
+    if param.dtype != torch.float32 or not param.is_contiguous():
+        raise _lib.PsoLibError("prodigy_step: param must be a contiguous float32 tensor")
+    wsb = lib().pso_prodigy_ws_bytes(n)
+    if state.ws is None or state.ws.numel() < wsb:
+        state.ws = torch.empty(wsb, device=param.device, dtype=torch.uint8)
+    flags = ((_lib.PRODIGY_DECOUPLE if decouple else 0) | (_lib.PRODIGY_BIAS_CORRECTION if use_bias_correction else 0)
+             | (_lib.PRODIGY_SAFEGUARD_WARMUP if safeguard_warmup else 0))
+    beta3 = math.sqrt(float(betas[1])) if beta3 is None else float(beta3)
+    check(lib().pso_prodigy_step(n, ptr(param), ptr(grad), ptr(state.p0), ptr(state.exp_avg), ptr(state.exp_avg_sq),
+                                 ptr(state.s), ptr(state.state), float(lr), float(betas[0]), float(betas[1]), beta3,
+                                 float(eps), float(weight_decay), flags, float(d_coef), float(growth_rate),
+                                 float(grad_scale), ptr(clip), ptr(amp_state), ptr(state.ws), state.ws.numel(),
+                                 stream_ptr()), "pso_prodigy_step")
 
 
 def zero_(x):

@@ -12,7 +12,9 @@
   buffer) is re-quantised into the per-tensor layout on load, with a warning.  A trainer with a loss scaler
   (`amp.LossScaler` or `amp.DeviceLossScaler`, fp16 training) also writes the scaler's `state_dict()` under the
   additive key `loss_scaler` of `pso_state.json`; a checkpoint without it loads as before and keeps the trainer's
-  scaler as constructed.
+  scaler as constructed.  A Prodigy trainer (`optimizer="prodigy"`) writes `p0`, `exp_avg`, `exp_avg_sq`, `s` and
+  the scalar state block `prodigy_state` instead, and `pso_state.json` names the optimizer under the additive key
+  `optimizer`; loading a checkpoint of the other optimizer raises `KeyError`.
 """
 import json
 import os
@@ -79,14 +81,18 @@ def save_state(trainer, output_dir):
     unet = trainer.unet
     save_lora_weights(output_dir, peft_to_diffusers(get_peft_model_state_dict(unet)))
     a8 = getattr(trainer, "adam8", None)
-    if a8 is not None:  # 8-bit AdamW state as it stands (codes + block absmax): a resume continues bit for bit
+    pro = getattr(trainer, "prodigy", None)
+    if pro is not None:  # Prodigy: p0, the moments, s and the scalar state block as they stand
+        opt = {k: v.cpu() for k, v in pro.tensors().items()}
+    elif a8 is not None:  # 8-bit AdamW state as it stands (codes + block absmax): a resume continues bit for bit
         opt = {k: v.cpu() for k, v in a8.tensors().items()}
     else:
         opt = {"exp_avg": trainer.exp_avg.cpu(), "exp_avg_sq": trainer.exp_avg_sq.cpu()}
     save_file(opt, os.path.join(output_dir, OPT_NAME),
               metadata={"step": str(trainer.opt_step), "n_micro": str(trainer.n_micro)})
     with open(os.path.join(output_dir, "pso_state.json"), "w") as f:
-        meta = {"opt_step": trainer.opt_step, "n_micro": trainer.n_micro, "rank": unet.lora.r}
+        meta = {"opt_step": trainer.opt_step, "n_micro": trainer.n_micro, "rank": unet.lora.r,
+                "optimizer": "prodigy" if pro is not None else "adamw8bit" if a8 is not None else "adamw"}
         scaler = getattr(trainer, "scaler", None)
         if scaler is not None:
             meta["loss_scaler"] = scaler.state_dict()
@@ -98,7 +104,15 @@ def load_state(trainer, input_dir):
     load_lora_into_unet(sd, alphas, trainer.unet)
     opt = load_file(os.path.join(input_dir, OPT_NAME))
     a8 = getattr(trainer, "adam8", None)
-    if a8 is not None:
+    pro = getattr(trainer, "prodigy", None)
+    if pro is None and "prodigy_state" in opt:
+        raise KeyError("checkpoint holds Prodigy state; this trainer runs AdamW (optimizer='adamw')")
+    if pro is not None:
+        if "prodigy_state" not in opt:
+            raise KeyError("checkpoint holds AdamW state; this trainer runs Prodigy (optimizer='prodigy')")
+        for k, t in pro.tensors().items():
+            t.copy_(opt[k])
+    elif a8 is not None:
         if "exp_avg_q" not in opt:
             raise KeyError("checkpoint holds fp32 AdamW state; this trainer runs the 8-bit AdamW (use_8bit_adam)")
         mine = a8.tensors()

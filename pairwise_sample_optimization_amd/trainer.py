@@ -275,6 +275,48 @@ class OptStep:
             tr.__dict__["opt_step"] = int(value)
 
 
+# the Prodigy arguments both trainers take (train.prodigy_* of a run config, --prodigy_* of the DreamBooth script)
+PRODIGY_KEYS = ("prodigy_beta3", "prodigy_decouple", "prodigy_use_bias_correction", "prodigy_safeguard_warmup",
+                "prodigy_d0", "prodigy_d_coef", "prodigy_growth_rate")
+
+
+def normalize_optimizer(name):
+    """'adamw' or 'prodigy' (case-insensitive, the DreamBooth script's --optimizer, DB:622-627)."""
+    opt = str(name).lower()
+    if opt not in ("adamw", "prodigy"):
+        raise ValueError(f"optimizer must be 'adamw' or 'prodigy', got {name!r}")
+    return opt
+
+
+def init_optimizer_state(tr, unet, optimizer="adamw", use_8bit_adam=False, prodigy_beta3=None, prodigy_decouple=True,
+                         prodigy_use_bias_correction=False, prodigy_safeguard_warmup=False, prodigy_d0=1e-6,
+                         prodigy_d_coef=1.0, prodigy_growth_rate=float("inf")):
+    """The optimizer state of a trainer over trainable(unet)'s flat master: tr.optimizer, and either the AdamW state
+    (tr.exp_avg / tr.exp_avg_sq, or tr.adam8 -- the blockwise 8-bit AdamW of bitsandbytes: uint8 codes + per-2048-block
+    absmax, blocks restarting at every parameter tensor, 32-bit state under 4096 elements, K.Adam8State) or Prodigy's
+    (tr.prodigy = K.ProdigyState, tr.prodigy_opts = the keyword arguments of K.prodigy_step; tr.exp_avg / exp_avg_sq
+    then name its moments).  Prodigy has no 8-bit form: use_8bit_adam is ignored with a warning (DB:1486-1490)."""
+    master, _, _ = trainable(unet)
+    tr.optimizer = normalize_optimizer(optimizer)
+    tr.prodigy = tr.prodigy_opts = None
+    if tr.optimizer == "prodigy":
+        if use_8bit_adam:
+            import warnings
+            warnings.warn("use_8bit_adam is ignored when optimizer is not set to 'AdamW' (it is 'prodigy')")
+        tr.adam8 = None
+        tr.prodigy = K.ProdigyState(master, d0=prodigy_d0)
+        tr.prodigy_opts = dict(beta3=prodigy_beta3, decouple=bool(prodigy_decouple),
+                               use_bias_correction=bool(prodigy_use_bias_correction),
+                               safeguard_warmup=bool(prodigy_safeguard_warmup), d_coef=float(prodigy_d_coef),
+                               growth_rate=float(prodigy_growth_rate))
+        tr.exp_avg, tr.exp_avg_sq = tr.prodigy.exp_avg, tr.prodigy.exp_avg_sq
+        return
+    tr.adam8 = K.Adam8State(master.numel(), master.device, segments=trainable_segments(unet)) \
+        if use_8bit_adam else None
+    tr.exp_avg = None if use_8bit_adam else torch.zeros_like(master)
+    tr.exp_avg_sq = None if use_8bit_adam else torch.zeros_like(master)
+
+
 def _amp_optimizer_step(tr, scaler, scale):
     """lora_optimizer_step after the all-reduce with a DeviceLossScaler: unscale / norm / clip -> AdamW -> scale
     update -> zero -> refresh, every decision (inf-skip, step count, back-off and growth) taken by the kernels on the
@@ -283,7 +325,10 @@ def _amp_optimizer_step(tr, scaler, scale):
     st = scaler.state
     K.amp_unscale_clip(grad, tr.max_grad_norm, st, tr.betas, grad_scale=scale)
     cast = True
-    if getattr(tr, "adam8", None) is not None:
+    if getattr(tr, "prodigy", None) is not None:
+        zeroed = False
+        K.prodigy_step(master, grad, tr.prodigy, tr.lr, tr.betas, tr.adam_eps, tr.wd, amp_state=st, **tr.prodigy_opts)
+    elif getattr(tr, "adam8", None) is not None:
         work = _work_copy(tr.unet, master)
         zeroed = K.adamw8bit_step_amp(master, grad, tr.adam8, tr.lr, tr.betas, tr.adam_eps, tr.wd, st, out_bf16=work,
                                       zero_grad=True)
@@ -328,7 +373,11 @@ def lora_optimizer_step(tr):
             return
     tr.opt_step += 1
     cast = True
-    if getattr(tr, "adam8", None) is not None:  # train.use_8bit_adam: bitsandbytes AdamW8bit (T:427-435)
+    if getattr(tr, "prodigy", None) is not None:  # optimizer="prodigy": k, d and dlr stay on the device
+        zeroed = False
+        K.prodigy_step(master, grad, tr.prodigy, tr.lr, tr.betas, tr.adam_eps, tr.wd, grad_scale=scale,
+                       clip=tr.clip_buf, **tr.prodigy_opts)
+    elif getattr(tr, "adam8", None) is not None:  # train.use_8bit_adam: bitsandbytes AdamW8bit (T:427-435)
         work = _work_copy(tr.unet, master)  # the step also writes the bf16 working copy (no separate cast pass)
         # with a per-tensor block table the step also zeroes the gradient it reads (the pads between tensors are
         # zero from allocation and no kernel writes them)
@@ -351,7 +400,9 @@ class PSOTrainer:
                  weight_decay=1e-6, adam_eps=1e-8, max_grad_norm=1.0, gradient_accumulation_steps=1,
                  train_batch_size=1, num_reward=1, process_group=None, max_pass_images=16, ref_unet=None,
                  latent_dtype=torch.float32, allreduce_dtype=None, use_8bit_adam=False, overlap_sync=None,
-                 bucket_mb=32.0, loss_scale=None):
+                 bucket_mb=32.0, loss_scale=None, optimizer="adamw", prodigy_beta3=None, prodigy_decouple=True,
+                 prodigy_use_bias_correction=False, prodigy_safeguard_warmup=False, prodigy_d0=1e-6,
+                 prodigy_d_coef=1.0, prodigy_growth_rate=float("inf")):
         self.unet = unet
         # loss_scale: None (no scaling), a float (initial scale), an amp.LossScaler or an amp.DeviceLossScaler (state
         # on the device, no sync in the optimizer step): dynamic loss scaling with inf-skip for fp16 training.
@@ -379,12 +430,12 @@ class PSOTrainer:
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         master, _, _ = trainable(unet)
         # optimizer state: fp32 AdamW moments, or -- train.use_8bit_adam, the reference default (T:427-435) -- the
-        # blockwise 8-bit AdamW of bitsandbytes (uint8 codes + per-2048-block absmax, blocks restarting at every
-        # parameter tensor, 32-bit state under 4096 elements: K.Adam8State)
-        self.adam8 = K.Adam8State(master.numel(), master.device, segments=trainable_segments(unet)) \
-            if use_8bit_adam else None
-        self.exp_avg = None if use_8bit_adam else torch.zeros_like(master)
-        self.exp_avg_sq = None if use_8bit_adam else torch.zeros_like(master)
+        # blockwise 8-bit AdamW of bitsandbytes, or -- optimizer="prodigy" (lr around 1.0) -- Prodigy's
+        init_optimizer_state(self, unet, optimizer=optimizer, use_8bit_adam=use_8bit_adam,
+                             prodigy_beta3=prodigy_beta3, prodigy_decouple=prodigy_decouple,
+                             prodigy_use_bias_correction=prodigy_use_bias_correction,
+                             prodigy_safeguard_warmup=prodigy_safeguard_warmup, prodigy_d0=prodigy_d0,
+                             prodigy_d_coef=prodigy_d_coef, prodigy_growth_rate=prodigy_growth_rate)
         self.opt_step = 0
         self.n_micro = 0
         self.clip_buf = torch.zeros(2, device=master.device, dtype=torch.float32)
@@ -469,7 +520,9 @@ class PSOTrainer:
                    adam_eps=tr.adam_epsilon, max_grad_norm=tr.max_grad_norm,
                    gradient_accumulation_steps=tr.gradient_accumulation_steps, train_batch_size=tr.batch_size,
                    num_reward=num_reward, process_group=process_group, ref_unet=ref_unet, latent_dtype=latent_dtype,
-                   use_8bit_adam=bool(getattr(tr, "use_8bit_adam", False)), loss_scale=loss_scale)
+                   use_8bit_adam=bool(getattr(tr, "use_8bit_adam", False)), loss_scale=loss_scale,
+                   optimizer=getattr(tr, "optimizer", "adamw"),
+                   **{k: getattr(tr, k) for k in PRODIGY_KEYS if hasattr(tr, k)})
 
     # ------------------------------------------------------------------------------------------------------------
     # coefficients of transition j (host float32 scalars, the reference's operation order)
