@@ -517,6 +517,51 @@ int pso_adamw8bit_step_blocks_zero_grad_amp(long n, int nblk, const long* desc, 
                                             float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, float lr,
                                             float beta1, float beta2, float eps, float weight_decay,
                                             const void* amp_state, void* stream);
+/* Learning-rate schedule with warm-up, evaluated on the device: the six lambdas of diffusers' optimization.py that the
+ * DreamBooth script reaches through get_scheduler(--lr_scheduler, --lr_warmup_steps, --lr_num_cycles, --lr_power)
+ * (DB:586-612, 1614-1621), stepped once per applied optimizer step (DB:1962-1963).  Parity with diffusers itself is
+ * unpinned (not installed here; transformers.optimization carries the same lambdas and is the CPU oracle).
+ * pso_lr_schedule: lr_out[0] = float32(base_lr * lambda(k)); one workgroup, one active lane, fp64 in the order of the
+ *   Python lambdas, rounded to fp32 once.  k = optimizer steps applied before this one:
+ *     amp_state == NULL  k = step - 1 (step counts from 1, as pso_adamw_step's)
+ *     amp_state != NULL  k = PSO_AMP_STEP - 1, read on the device after pso_amp_unscale_clip has advanced it; with
+ *                        FOUND_INF set lr_out is left untouched (a skipped step does not advance the schedule)
+ *   w = warmup, T = total; k < w (every kind but PSO_LR_CONSTANT): lambda = k / max(1, w); otherwise
+ *     PSO_LR_CONSTANT, PSO_LR_CONSTANT_WITH_WARMUP  1
+ *     PSO_LR_LINEAR                 max(0, (T - k) / max(1, T - w))
+ *     PSO_LR_COSINE                 max(0, 0.5 (1 + cos(pi p))), p = (k - w) / max(1, T - w); num_cycles is not read
+ *                                   (get_scheduler leaves it at 0.5), and the curve rises again for k > T
+ *     PSO_LR_COSINE_WITH_RESTARTS   0 for p >= 1, else max(0, 0.5 (1 + cos(pi ((num_cycles p) mod 1))))
+ *     PSO_LR_POLYNOMIAL             lr_end / base_lr for k > T, else ((base_lr - lr_end) (1 - (k - w) / (T - w))^power
+ *                                   + lr_end) / base_lr, lr_end = 1e-7
+ *   World size cancels (the script scales w and T by num_processes, accelerate steps the scheduler num_processes times
+ *   per optimizer step): pass the unscaled counts.  PSO_ERR_ARG: unknown kind, lr_out NULL, base_lr <= 0, step < 1
+ *   without a state, warmup < 0, polynomial with total <= warmup or base_lr <= 1e-7.
+ * pso_adamw_step_amp_lr / pso_adamw8bit_step_blocks[_zero_grad]_amp_lr: = their _amp siblings above with the step's lr
+ *   read from the device word lr_dev (4-B aligned; what pso_lr_schedule wrote) once per thread in place of the float
+ *   argument -- the same bits for the same fp32 value.  0 is legal: the moments / codes move, the parameters keep
+ *   their bits. */
+#define PSO_LR_CONSTANT 0
+#define PSO_LR_CONSTANT_WITH_WARMUP 1
+#define PSO_LR_LINEAR 2
+#define PSO_LR_COSINE 3
+#define PSO_LR_COSINE_WITH_RESTARTS 4
+#define PSO_LR_POLYNOMIAL 5
+int pso_lr_schedule(int kind, double base_lr, int warmup, int total, int num_cycles, double power,
+                    const void* amp_state, int step, float* lr_out, void* stream);
+int pso_adamw_step_amp_lr(long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                          const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
+                          const void* amp_state, void* stream);
+int pso_adamw8bit_step_blocks_amp_lr(long n, int nblk, const long* desc, float* param, void* param_bf16,
+                                     const float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
+                                     float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, const float* lr_dev,
+                                     float beta1, float beta2, float eps, float weight_decay, const void* amp_state,
+                                     void* stream);
+int pso_adamw8bit_step_blocks_zero_grad_amp_lr(long n, int nblk, const long* desc, float* param, void* param_bf16,
+                                               float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q,
+                                               float* absmax_m, float* absmax_v, float* exp_avg_32,
+                                               float* exp_avg_sq_32, const float* lr_dev, float beta1, float beta2,
+                                               float eps, float weight_decay, const void* amp_state, void* stream);
 /* Prodigy (prodigyopt 1.0's Prodigy.step, one parameter group): the DreamBooth script's --optimizer prodigy, DB:622-673
  * (its own branch, DB:1479-1510, validates the flags and never builds the optimizer).  Parity with the package is
  * unpinned (prodigyopt is not available here; tests/prodigy_ref.py restates the arithmetic below).  Per-element state on
@@ -554,7 +599,11 @@ int pso_adamw8bit_step_blocks_zero_grad_amp(long n, int nblk, const long* desc, 
  * beta3: prodigyopt's default is sqrt(beta2), which the caller passes.  growth_rate may be +inf.
  * amp_state (may be NULL): the loss-scaler block above.  FOUND_INF set: param, exp_avg, exp_avg_sq, s and the state are
  * left untouched except SKIPPED += 1; otherwise g = grad * GRAD_MUL * CLIP_COEF and grad_scale / clip_coef are not
- * read.  PSO_ERR_ARG: n <= 0, a null buffer, ws_bytes < pso_prodigy_ws_bytes(n), lr <= 0, unknown flags. */
+ * read.  PSO_ERR_ARG: n <= 0, a null buffer, ws_bytes < pso_prodigy_ws_bytes(n), lr <= 0, unknown flags.
+ * pso_prodigy_step_lr: the same step with lr read from the device word lr_dev (4-B aligned, not NULL; what
+ * pso_lr_schedule wrote) once per thread -- the same bits for the same fp32 value; amp_state may be NULL as above.  A
+ * word of 0 is legal (every warm-up starts there) and follows the restatement with dlr = 0: m and v move, s moves with
+ * PSO_PRODIGY_SAFEGUARD_WARMUP only, and without it a first step ends at den == 0 with p, d and k as they were. */
 #define PSO_PRODIGY_WORDS 24
 #define PSO_PRODIGY_D 0
 #define PSO_PRODIGY_D0 2
@@ -574,6 +623,10 @@ int pso_prodigy_step(long n, float* param, const float* grad, const float* p0, f
                      float* s, void* state, float lr, float beta1, float beta2, float beta3, float eps,
                      float weight_decay, int flags, float d_coef, float growth_rate, float grad_scale,
                      const float* clip_coef, const void* amp_state, void* ws, size_t ws_bytes, void* stream);
+int pso_prodigy_step_lr(long n, float* param, const float* grad, const float* p0, float* exp_avg, float* exp_avg_sq,
+                        float* s, void* state, const float* lr_dev, float beta1, float beta2, float beta3, float eps,
+                        float weight_decay, int flags, float d_coef, float growth_rate, float grad_scale,
+                        const float* clip_coef, const void* amp_state, void* ws, size_t ws_bytes, void* stream);
 int pso_preference(int P, int m, const float* rewards, const int64_t* reward_idx, int mode, float* pref,
                    void* stream);
 

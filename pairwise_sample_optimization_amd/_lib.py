@@ -41,6 +41,9 @@ PRODIGY_WORDS = 24
 PRODIGY_F64 = {"d": 0, "d0": 2, "d_max": 4, "d_numerator": 6, "d_denom": 8, "d_hat": 10, "dlr": 12}
 PRODIGY_I32 = {"k": 14, "updated": 15, "skipped": 16}
 PRODIGY_DECOUPLE, PRODIGY_BIAS_CORRECTION, PRODIGY_SAFEGUARD_WARMUP = 1, 2, 4
+# kinds of pso_lr_schedule (include/pso_amd.h PSO_LR_*): the --lr_scheduler names the DreamBooth script offers
+LR_KINDS = {"constant": 0, "constant_with_warmup": 1, "linear": 2, "cosine": 3, "cosine_with_restarts": 4,
+            "polynomial": 5}
 
 _lib = None
 
@@ -54,6 +57,7 @@ class PsoTnRankProblem(ctypes.Structure):
 vp = ctypes.c_void_p
 ci = ctypes.c_int
 cf = ctypes.c_float
+cd = ctypes.c_double
 csz = ctypes.c_size_t
 ci64 = ctypes.c_int64
 cl = ctypes.c_long
@@ -160,6 +164,14 @@ SIGNATURES = {
                                            vp]),
     "pso_adamw8bit_step_blocks_zero_grad_amp": (ci, [cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf,
                                                      cf, vp, vp]),
+    "pso_lr_schedule": (ci, [ci, cd, ci, ci, ci, cd, vp, ci, vp, vp]),
+    "pso_adamw_step_amp_lr": (ci, [cl, vp, vp, vp, vp, vp, cf, cf, cf, cf, vp, vp]),
+    "pso_adamw8bit_step_blocks_amp_lr": (ci, [cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, vp,
+                                              vp]),
+    "pso_adamw8bit_step_blocks_zero_grad_amp_lr": (ci, [cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf,
+                                                        cf, vp, vp]),
+    "pso_prodigy_step_lr": (ci, [cl, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, cf, cf, vp, vp, vp,
+                                 csz, vp]),
     "pso_prodigy_ws_bytes": (csz, [cl]),
     "pso_prodigy_step": (ci, [cl, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, cf, ci, cf, cf, cf, vp, vp, vp, csz,
                               vp]),

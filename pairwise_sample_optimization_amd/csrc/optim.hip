@@ -133,6 +133,51 @@ __global__ void amp_update_kernel(float* __restrict__ st, float growth, float ba
   st[PSO_AMP_INV_SCALE] = 1.0f / scale;
 }
 
+// ---- learning-rate schedule (diffusers' optimization.py lambdas behind get_scheduler, DB:1614-1621; stepped once per
+// applied optimizer step, DB:1962-1963): lr_out[0] = float32(base_lr * lambda(k)), the arithmetic in fp64 in the order
+// of the Python lambdas, contraction off.  k = the optimizer steps applied BEFORE this one: step - 1 from the argument,
+// or -- with the loss-scaler state -- PSO_AMP_STEP - 1 after pso_amp_unscale_clip has advanced it; a skipped step
+// (FOUND_INF) leaves lr_out as it was, so the schedule does not advance (accelerate's scheduler wrapper skips with the
+// optimizer).  World size cancels: the script scales warm-up and total steps by num_processes and accelerate steps the
+// scheduler num_processes times per optimizer step, so every quotient below is the same rational number and every
+// rank evaluates lambda with the unscaled counts.  One lane.
+__global__ void lr_schedule_kernel(int kind, double base_lr, int warmup, int total, int cycles, double power,
+                                   const int* __restrict__ amp, int step, float* __restrict__ lr_out) {
+#pragma clang fp contract(off)
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  int k = step - 1;
+  if (amp) {
+    if (amp[PSO_AMP_FOUND_INF]) return;
+    k = amp[PSO_AMP_STEP] - 1;
+  }
+  if (k < 0) k = 0;
+  const double pi = 3.141592653589793;  // math.pi
+  double lam = 1.0;
+  if (kind != PSO_LR_CONSTANT && k < warmup) {
+    lam = (double)k / (double)max(1, warmup);
+  } else if (kind == PSO_LR_LINEAR) {
+    const double x = (double)(total - k) / (double)max(1, total - warmup);
+    lam = x > 0.0 ? x : 0.0;
+  } else if (kind == PSO_LR_COSINE || kind == PSO_LR_COSINE_WITH_RESTARTS) {
+    const double p = (double)(k - warmup) / (double)max(1, total - warmup);
+    double x;
+    if (kind == PSO_LR_COSINE)  // num_cycles stays 0.5 (get_scheduler does not pass it); rises again past `total`
+      x = 0.5 * (1.0 + cos(((pi * 0.5) * 2.0) * p));
+    else
+      x = p >= 1.0 ? 0.0 : 0.5 * (1.0 + cos(pi * fmod((double)cycles * p, 1.0)));
+    lam = x > 0.0 ? x : 0.0;
+  } else if (kind == PSO_LR_POLYNOMIAL) {
+    const double lr_end = 1e-7;
+    if (k > total) {
+      lam = lr_end / base_lr;
+    } else {
+      const double pct = 1.0 - (double)(k - warmup) / (double)(total - warmup);
+      lam = ((base_lr - lr_end) * pow(pct, power) + lr_end) / base_lr;
+    }
+  }
+  lr_out[0] = (float)(base_lr * lam);
+}
+
 // s = the factor on the gradient read (1/world, 1/loss-scale and the clip coefficient folded together)
 __device__ __forceinline__ void adamw_body(long n, float* __restrict__ p, const float* __restrict__ g,
                                            float* __restrict__ m, float* __restrict__ v, float lr, float b1, float b2,
@@ -163,6 +208,16 @@ __global__ void adamw_amp_kernel(long n, float* __restrict__ p, const float* __r
                                  const float* __restrict__ st) {
   if (AMP_CI(st, PSO_AMP_FOUND_INF)) return;  // skipped step: parameters and moments untouched
   adamw_body(n, p, g, m, v, lr, b1, b2, eps, wd, st[PSO_AMP_BC1], st[PSO_AMP_BC2_SQRT],
+             st[PSO_AMP_GRAD_MUL] * st[PSO_AMP_CLIP_COEF]);
+}
+
+// ... and with the step's learning rate read from a device word (pso_lr_schedule wrote it); 0 is legal: the moments
+// move, the parameters keep their bits
+__global__ void adamw_amp_lr_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                    float* __restrict__ v, const float* __restrict__ lr_dev, float b1, float b2,
+                                    float eps, float wd, const float* __restrict__ st) {
+  if (AMP_CI(st, PSO_AMP_FOUND_INF)) return;
+  adamw_body(n, p, g, m, v, lr_dev[0], b1, b2, eps, wd, st[PSO_AMP_BC1], st[PSO_AMP_BC2_SQRT],
              st[PSO_AMP_GRAD_MUL] * st[PSO_AMP_CLIP_COEF]);
 }
 
@@ -401,6 +456,17 @@ __global__ __launch_bounds__(256) void adamw8bit_kernel(
 // the per-tensor step with the gradient factor, c1 / c2 and the inf-skip read from the loss-scaler state.  A skipped
 // step leaves the parameters, codes, absmax, 32-bit state and working copy untouched; with zero_grad it still zeroes
 // the gradient elements its blocks cover (the host path zeroes the gradient of a skipped step too).
+// the skipped step of the two kernels below; true when the step is skipped (uniform over the workgroup)
+__device__ __forceinline__ bool adam8_amp_skip(const float* __restrict__ st, float* g, const long* __restrict__ desc,
+                                               int zero_grad) {
+  if (!AMP_CI(st, PSO_AMP_FOUND_INF)) return false;
+  if (zero_grad) {
+    const long base = desc[4 * (long)blockIdx.x], end = base + desc[4 * (long)blockIdx.x + 1];
+    for (long i = base + threadIdx.x; i < end; i += blockDim.x) g[i] = 0.f;
+  }
+  return true;
+}
+
 template <int LAY>
 __global__ __launch_bounds__(256) void adamw8bit_amp_kernel(
     long n, float* __restrict__ p, float* g, uint8_t* __restrict__ qm, uint8_t* __restrict__ qv,
@@ -408,15 +474,27 @@ __global__ __launch_bounds__(256) void adamw8bit_amp_kernel(
     float decay, const float* __restrict__ st, bf16_t* __restrict__ pw, const long* __restrict__ desc,
     float* __restrict__ m32, float* __restrict__ v32, int zero_grad, Adam8Maps maps) {
 #pragma clang fp contract(off)
-  if (AMP_CI(st, PSO_AMP_FOUND_INF)) {
-    if (zero_grad) {
-      const long base = desc[4 * (long)blockIdx.x], end = base + desc[4 * (long)blockIdx.x + 1];
-      for (long i = base + threadIdx.x; i < end; i += blockDim.x) g[i] = 0.f;
-    }
-    return;
-  }
+  if (adam8_amp_skip(st, g, desc, zero_grad)) return;
   const float c1 = st[PSO_AMP_C1], c2 = st[PSO_AMP_C2];
   const float step_size = (-lr) * c2 / c1;  // adam8_launch's host expressions, in fp32 as there
+  adamw8bit_body<LAY>(n, p, g, qm, qv, am, av, b1, omb1, b2, omb2, c2 * eps, step_size, decay,
+                      st[PSO_AMP_GRAD_MUL] * st[PSO_AMP_CLIP_COEF], pw, desc, m32, v32, zero_grad, maps);
+}
+
+// ... and with the step's learning rate read from a device word: step_size and the decay factor, which adam8_launch
+// forms on the host from its lr argument, are formed here by the same expressions (the decay in double, as there)
+template <int LAY>
+__global__ __launch_bounds__(256) void adamw8bit_amp_lr_kernel(
+    long n, float* __restrict__ p, float* g, uint8_t* __restrict__ qm, uint8_t* __restrict__ qv,
+    float* __restrict__ am, float* __restrict__ av, float b1, float omb1, float b2, float omb2, float eps,
+    const float* __restrict__ lr_dev, float wd, const float* __restrict__ st, bf16_t* __restrict__ pw,
+    const long* __restrict__ desc, float* __restrict__ m32, float* __restrict__ v32, int zero_grad, Adam8Maps maps) {
+#pragma clang fp contract(off)
+  if (adam8_amp_skip(st, g, desc, zero_grad)) return;
+  const float lr = lr_dev[0];
+  const float c1 = st[PSO_AMP_C1], c2 = st[PSO_AMP_C2];
+  const float step_size = (-lr) * c2 / c1;
+  const float decay = (float)(1.0 - (double)lr * wd);
   adamw8bit_body<LAY>(n, p, g, qm, qv, am, av, b1, omb1, b2, omb2, c2 * eps, step_size, decay,
                       st[PSO_AMP_GRAD_MUL] * st[PSO_AMP_CLIP_COEF], pw, desc, m32, v32, zero_grad, maps);
 }
@@ -539,6 +617,34 @@ int pso_adamw_step_amp(long n, float* param, const float* grad, float* exp_avg, 
   return pso_check_launch("pso_adamw_step_amp");
 }
 
+int pso_adamw_step_amp_lr(long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                          const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
+                          const void* amp_state, void* stream) {
+  PSO_ARG_CHECK(param && grad && exp_avg && exp_avg_sq && amp_state && ((uintptr_t)amp_state & 3) == 0 && lr_dev &&
+                    ((uintptr_t)lr_dev & 3) == 0,
+                "pso_adamw_step_amp_lr: bad args");
+  adamw_amp_lr_kernel<<<nblocks(n), OPT_THREADS, 0, (hipStream_t)stream>>>(n, param, grad, exp_avg, exp_avg_sq, lr_dev,
+                                                                           beta1, beta2, eps, weight_decay,
+                                                                           (const float*)amp_state);
+  return pso_check_launch("pso_adamw_step_amp_lr");
+}
+
+int pso_lr_schedule(int kind, double base_lr, int warmup, int total, int num_cycles, double power,
+                    const void* amp_state, int step, float* lr_out, void* stream) {
+  PSO_ARG_CHECK(kind >= PSO_LR_CONSTANT && kind <= PSO_LR_POLYNOMIAL, "pso_lr_schedule: unknown kind %d", kind);
+  PSO_ARG_CHECK(lr_out && ((uintptr_t)lr_out & 3) == 0 && ((uintptr_t)amp_state & 3) == 0,
+                "pso_lr_schedule: lr_out must be a 4-B aligned device word (amp_state 4-B aligned or NULL)");
+  PSO_ARG_CHECK(base_lr > 0.0, "pso_lr_schedule: base_lr must be positive, got %g", base_lr);
+  PSO_ARG_CHECK(amp_state || step >= 1, "pso_lr_schedule: step counts from 1 (got %d) when no amp_state is given",
+                step);
+  PSO_ARG_CHECK(warmup >= 0, "pso_lr_schedule: warmup %d < 0", warmup);
+  PSO_ARG_CHECK(kind != PSO_LR_POLYNOMIAL || (total > warmup && base_lr > 1e-7),
+                "pso_lr_schedule: polynomial needs total > warmup and base_lr > lr_end = 1e-7");
+  lr_schedule_kernel<<<1, 64, 0, (hipStream_t)stream>>>(kind, base_lr, warmup, total, num_cycles, power,
+                                                       (const int*)amp_state, step, lr_out);
+  return pso_check_launch("pso_lr_schedule");
+}
+
 size_t pso_adamw8bit_blocks(long n) { return (size_t)((n + ADAM8_BLOCK - 1) / ADAM8_BLOCK); }
 
 void pso_adamw8bit_maps(float* signed_map, float* unsigned_map) {
@@ -549,7 +655,8 @@ void pso_adamw8bit_maps(float* signed_map, float* unsigned_map) {
 static int adam8_launch(long n, int nblk, float* param, void* param_bf16, float* grad, int zero_grad, uint8_t* exp_avg_q,
                         uint8_t* exp_avg_sq_q, float* absmax_m, float* absmax_v, const long* desc, float* m32,
                         float* v32, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                        float grad_scale, const float* clip_coef, void* stream, const float* amp = nullptr) {
+                        float grad_scale, const float* clip_coef, void* stream, const float* amp = nullptr,
+                        const float* lr_dev = nullptr) {
   static Adam8Maps maps = [] {
     Adam8Maps m;
     adam8_dynamic_map(true, m.s);
@@ -557,7 +664,8 @@ static int adam8_launch(long n, int nblk, float* param, void* param_bf16, float*
     return m;
   }();
   // amp != nullptr: step, grad_scale and clip_coef are unused -- c1 / c2, the gradient factor and the inf-skip come
-  // from the loss-scaler state on the device (adamw8bit_amp_kernel)
+  // from the loss-scaler state on the device (adamw8bit_amp_kernel); lr_dev != nullptr (with amp): lr is unused too --
+  // the device word holds it (adamw8bit_amp_lr_kernel)
   const double b1 = beta1, b2 = beta2;
   const float c1 = (float)(1.0 - std::pow(b1, step));
   const float c2 = (float)std::sqrt(1.0 - std::pow(b2, step));
@@ -581,6 +689,12 @@ static int adam8_launch(long n, int nblk, float* param, void* param_bf16, float*
 #define PSO_ADAM8_AMP_ARGS                                                                                               \
   n, param, grad, exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, beta1, omb1, beta2, omb2, eps, lr, decay, amp,            \
       (bf16_t*)param_bf16, desc, m32, v32, zero_grad, maps
+  if (amp && lr_dev) {
+    adamw8bit_amp_lr_kernel<ADAM8_LAYOUT_DEFAULT><<<nblk, 256, 0, st>>>(
+        n, param, grad, exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, beta1, omb1, beta2, omb2, eps, lr_dev,
+        weight_decay, amp, (bf16_t*)param_bf16, desc, m32, v32, zero_grad, maps);
+    return pso_check_launch("pso_adamw8bit_step_amp_lr");
+  }
   if (amp) {
     adamw8bit_amp_kernel<ADAM8_LAYOUT_DEFAULT><<<nblk, 256, 0, st>>>(PSO_ADAM8_AMP_ARGS);
     return pso_check_launch("pso_adamw8bit_step_amp");
@@ -615,7 +729,7 @@ static int adam8_blocks(const char* who, long n, int nblk, const long* desc, flo
                         float* grad, int zero_grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
                         float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, float lr, float beta1, float beta2,
                         float eps, float weight_decay, int step, float grad_scale, const float* clip_coef,
-                        void* stream, const float* amp = nullptr) {
+                        void* stream, const float* amp = nullptr, const float* lr_dev = nullptr) {
   PSO_ARG_CHECK(param && grad && exp_avg_q && exp_avg_sq_q && absmax_m && absmax_v && step >= 1 && n > 0 &&
                     nblk >= 0 && (nblk == 0 || desc),
                 "%s: bad args", who);
@@ -624,7 +738,7 @@ static int adam8_blocks(const char* who, long n, int nblk, const long* desc, flo
                 "%s: param / grad / param_bf16 / 32-bit state need 16-B, the code arrays 8-B alignment", who);
   return adam8_launch(n, nblk, param, param_bf16, grad, zero_grad, exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, desc,
                       exp_avg_32, exp_avg_sq_32, lr, beta1, beta2, eps, weight_decay, step, grad_scale, clip_coef,
-                      stream, amp);
+                      stream, amp, lr_dev);
 }
 
 int pso_adamw8bit_step_blocks(long n, int nblk, const long* desc, float* param, void* param_bf16, const float* grad,
@@ -665,6 +779,30 @@ int pso_adamw8bit_step_blocks_zero_grad_amp(long n, int nblk, const long* desc, 
   return adam8_blocks("pso_adamw8bit_step_blocks_zero_grad_amp", n, nblk, desc, param, param_bf16, grad, 1, exp_avg_q,
                       exp_avg_sq_q, absmax_m, absmax_v, exp_avg_32, exp_avg_sq_32, lr, beta1, beta2, eps,
                       weight_decay, 1, 1.0f, nullptr, stream, (const float*)amp_state);
+}
+
+int pso_adamw8bit_step_blocks_amp_lr(long n, int nblk, const long* desc, float* param, void* param_bf16,
+                                     const float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
+                                     float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, const float* lr_dev,
+                                     float beta1, float beta2, float eps, float weight_decay, const void* amp_state,
+                                     void* stream) {
+  PSO_ARG_CHECK(amp_state && ((uintptr_t)amp_state & 3) == 0 && lr_dev && ((uintptr_t)lr_dev & 3) == 0,
+                "pso_adamw8bit_step_blocks_amp_lr: no amp_state or no lr_dev (4-B aligned)");
+  return adam8_blocks("pso_adamw8bit_step_blocks_amp_lr", n, nblk, desc, param, param_bf16, const_cast<float*>(grad),
+                      0, exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, exp_avg_32, exp_avg_sq_32, 0.0f, beta1, beta2,
+                      eps, weight_decay, 1, 1.0f, nullptr, stream, (const float*)amp_state, lr_dev);
+}
+
+int pso_adamw8bit_step_blocks_zero_grad_amp_lr(long n, int nblk, const long* desc, float* param, void* param_bf16,
+                                               float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q,
+                                               float* absmax_m, float* absmax_v, float* exp_avg_32,
+                                               float* exp_avg_sq_32, const float* lr_dev, float beta1, float beta2,
+                                               float eps, float weight_decay, const void* amp_state, void* stream) {
+  PSO_ARG_CHECK(amp_state && ((uintptr_t)amp_state & 3) == 0 && lr_dev && ((uintptr_t)lr_dev & 3) == 0,
+                "pso_adamw8bit_step_blocks_zero_grad_amp_lr: no amp_state or no lr_dev (4-B aligned)");
+  return adam8_blocks("pso_adamw8bit_step_blocks_zero_grad_amp_lr", n, nblk, desc, param, param_bf16, grad, 1,
+                      exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, exp_avg_32, exp_avg_sq_32, 0.0f, beta1, beta2, eps,
+                      weight_decay, 1, 1.0f, nullptr, stream, (const float*)amp_state, lr_dev);
 }
 
 int pso_adamw8bit_step(long n, float* param, const float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q,

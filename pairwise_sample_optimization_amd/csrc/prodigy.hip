@@ -13,6 +13,8 @@
 // The per-element arithmetic is fp32 with contraction off, in the order of the restatement; every scalar that enters
 // it is formed in fp64 from the block and rounded to fp32 once.  The partial sums are per-thread strided, then wave and
 // workgroup trees, then the fixed-order sum of finalise: a step gives the same bits from run to run.
+// pso_prodigy_step_lr is the same three launches with lr read from a device word (the learning-rate schedule,
+// pso_lr_schedule in optim.hip): pass 1 and finalise load it once per thread in place of the argument.
 #include "common.h"
 
 #include <cmath>
@@ -70,9 +72,11 @@ __device__ __forceinline__ void prodigy_elem1(const ProdigyCoef& c, float graw, 
 __global__ __launch_bounds__(PRO_THREADS) void prodigy_pass1_kernel(
     long n, const float* __restrict__ p, const float* __restrict__ g, const float* __restrict__ p0,
     float* __restrict__ m, float* __restrict__ v, float* __restrict__ s, const void* __restrict__ st, ProdigyHyper h,
-    float gscale, const float* __restrict__ clip, const float* __restrict__ amp, double* __restrict__ part) {
+    float gscale, const float* __restrict__ clip, const float* __restrict__ amp, const float* __restrict__ lr_dev,
+    double* __restrict__ part) {
 #pragma clang fp contract(off)
   if (prodigy_skip(amp)) return;
+  if (lr_dev) h.lr = lr_dev[0];  // pso_prodigy_step_lr: the step's lr from the device word (0 is legal: dlr = 0)
   __shared__ double red[2][PRO_THREADS / 64];
   const double d = PRO_CD(st, PSO_PRODIGY_D), d0 = PRO_CD(st, PSO_PRODIGY_D0);
   const double dlr = prodigy_dlr(st, h);
@@ -139,12 +143,14 @@ __global__ __launch_bounds__(PRO_THREADS) void prodigy_pass1_kernel(
 // then wave and workgroup trees), then thread 0 updates the state block
 __global__ __launch_bounds__(PRO_THREADS) void prodigy_finalise_kernel(int nparts, const double* __restrict__ part,
                                                                        void* __restrict__ st, ProdigyHyper h,
-                                                                       const float* __restrict__ amp) {
+                                                                       const float* __restrict__ amp,
+                                                                       const float* __restrict__ lr_dev) {
 #pragma clang fp contract(off)
   if (prodigy_skip(amp)) {
     if (threadIdx.x == 0) PRO_I(st, PSO_PRODIGY_SKIPPED) += 1;
     return;
   }
+  if (lr_dev) h.lr = lr_dev[0];
   __shared__ double red[2][PRO_THREADS / 64];
   double a = 0.0, b = 0.0;
   for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
@@ -234,32 +240,53 @@ extern "C" {
 
 size_t pso_prodigy_ws_bytes(long n) { return 2 * PRO_MAX_BLOCKS * sizeof(double); }
 
-int pso_prodigy_step(long n, float* param, const float* grad, const float* p0, float* exp_avg, float* exp_avg_sq,
-                     float* s, void* state, float lr, float beta1, float beta2, float beta3, float eps,
-                     float weight_decay, int flags, float d_coef, float growth_rate, float grad_scale,
-                     const float* clip_coef, const void* amp_state, void* ws, size_t ws_bytes, void* stream) {
+// lr_dev != nullptr: the kernels read the step's lr from that device word and `lr` is not used
+static int prodigy_launch(const char* who, long n, float* param, const float* grad, const float* p0, float* exp_avg,
+                          float* exp_avg_sq, float* s, void* state, float lr, const float* lr_dev, float beta1,
+                          float beta2, float beta3, float eps, float weight_decay, int flags, float d_coef,
+                          float growth_rate, float grad_scale, const float* clip_coef, const void* amp_state, void* ws,
+                          size_t ws_bytes, void* stream) {
   PSO_ARG_CHECK(n > 0 && param && grad && p0 && exp_avg && exp_avg_sq && s && state && ws,
-                "pso_prodigy_step: bad args (n <= 0 or a null pointer)");
-  PSO_ARG_CHECK(ws_bytes >= pso_prodigy_ws_bytes(n), "pso_prodigy_step: workspace of %zu bytes, need %zu", ws_bytes,
+                "%s: bad args (n <= 0 or a null pointer)", who);
+  PSO_ARG_CHECK(ws_bytes >= pso_prodigy_ws_bytes(n), "%s: workspace of %zu bytes, need %zu", who, ws_bytes,
                 pso_prodigy_ws_bytes(n));
-  PSO_ARG_CHECK(lr > 0.0f, "pso_prodigy_step: lr must be positive, got %g", (double)lr);
   PSO_ARG_CHECK(((uintptr_t)state & 7) == 0 && ((uintptr_t)ws & 7) == 0 && ((uintptr_t)amp_state & 3) == 0 &&
                     (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)p0 | (uintptr_t)exp_avg |
-                      (uintptr_t)exp_avg_sq | (uintptr_t)s | (uintptr_t)clip_coef) & 3) == 0,
-                "pso_prodigy_step: state / ws need 8-B, every other buffer 4-B alignment");
+                      (uintptr_t)exp_avg_sq | (uintptr_t)s | (uintptr_t)clip_coef | (uintptr_t)lr_dev) & 3) == 0,
+                "%s: state / ws need 8-B, every other buffer 4-B alignment", who);
   PSO_ARG_CHECK((flags & ~(PSO_PRODIGY_DECOUPLE | PSO_PRODIGY_BIAS_CORRECTION | PSO_PRODIGY_SAFEGUARD_WARMUP)) == 0,
-                "pso_prodigy_step: unknown flags 0x%x", flags);
+                "%s: unknown flags 0x%x", who, flags);
   const hipStream_t st = (hipStream_t)stream;
   const ProdigyHyper h = {lr, beta1, beta2, beta3, eps, weight_decay, d_coef, growth_rate, flags};
   const float* amp = (const float*)amp_state;
   const int nb = prodigy_blocks(n);
   // weight decay 0 takes neither decay branch (cwd / wd_g == 0)
   prodigy_pass1_kernel<<<nb, PRO_THREADS, 0, st>>>(n, param, grad, p0, exp_avg, exp_avg_sq, s, state, h, grad_scale,
-                                                  clip_coef, amp, (double*)ws);
-  prodigy_finalise_kernel<<<1, PRO_THREADS, 0, st>>>(nb, (const double*)ws, state, h, amp);
+                                                  clip_coef, amp, lr_dev, (double*)ws);
+  prodigy_finalise_kernel<<<1, PRO_THREADS, 0, st>>>(nb, (const double*)ws, state, h, amp, lr_dev);
   prodigy_pass2_kernel<<<nb, PRO_THREADS, 0, st>>>(n, param, exp_avg, exp_avg_sq, state, eps, weight_decay, flags,
                                                   amp);
-  return pso_check_launch("pso_prodigy_step");
+  return pso_check_launch(who);
+}
+
+int pso_prodigy_step(long n, float* param, const float* grad, const float* p0, float* exp_avg, float* exp_avg_sq,
+                     float* s, void* state, float lr, float beta1, float beta2, float beta3, float eps,
+                     float weight_decay, int flags, float d_coef, float growth_rate, float grad_scale,
+                     const float* clip_coef, const void* amp_state, void* ws, size_t ws_bytes, void* stream) {
+  PSO_ARG_CHECK(lr > 0.0f, "pso_prodigy_step: lr must be positive, got %g", (double)lr);
+  return prodigy_launch("pso_prodigy_step", n, param, grad, p0, exp_avg, exp_avg_sq, s, state, lr, nullptr, beta1,
+                        beta2, beta3, eps, weight_decay, flags, d_coef, growth_rate, grad_scale, clip_coef, amp_state,
+                        ws, ws_bytes, stream);
+}
+
+int pso_prodigy_step_lr(long n, float* param, const float* grad, const float* p0, float* exp_avg, float* exp_avg_sq,
+                        float* s, void* state, const float* lr_dev, float beta1, float beta2, float beta3, float eps,
+                        float weight_decay, int flags, float d_coef, float growth_rate, float grad_scale,
+                        const float* clip_coef, const void* amp_state, void* ws, size_t ws_bytes, void* stream) {
+  PSO_ARG_CHECK(lr_dev, "pso_prodigy_step_lr: no lr_dev");
+  return prodigy_launch("pso_prodigy_step_lr", n, param, grad, p0, exp_avg, exp_avg_sq, s, state, 0.0f, lr_dev, beta1,
+                        beta2, beta3, eps, weight_decay, flags, d_coef, growth_rate, grad_scale, clip_coef, amp_state,
+                        ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -30,24 +30,29 @@ from . import _lib
 from . import kernels as K
 from .amp import DeviceLossScaler, LossScaler, make_scaler
 from .schedulers import EulerDiscreteScheduler, db_distill_timesteps
-from .trainer import OptStep, init_optimizer_state, lora_optimizer_step
+from .trainer import LastLr, OptStep, init_lr_schedule, init_optimizer_state, lora_optimizer_step
 
 
 class DreamBoothPSOTrainer:
     opt_step = OptStep()
+    last_lr = LastLr()
 
     def __init__(self, unet, vae, loss_type="pso_db", beta_pso=5.0, neg_defactor=0.1, prior_loss_weight=0.5,
                  distill_train_timesteps=4, learning_rate=2e-4, betas=(0.9, 0.999), adam_weight_decay=1e-4,
                  adam_epsilon=1e-8, max_grad_norm=1.0, gradient_accumulation_steps=4, process_group=None,
                  loss_scale=None, use_8bit_adam=False, optimizer="adamw", prodigy_beta3=None, prodigy_decouple=True,
                  prodigy_use_bias_correction=False, prodigy_safeguard_warmup=False, prodigy_d0=1e-6,
-                 prodigy_d_coef=1.0, prodigy_growth_rate=float("inf")):
+                 prodigy_d_coef=1.0, prodigy_growth_rate=float("inf"), lr_scheduler="constant", lr_warmup_steps=0,
+                 max_train_steps=None, lr_num_cycles=1, lr_power=1.0):
         """Defaults: DB argparse defaults (DB:636-674, 757-777) overridden by the recipe scripts/pso_dog.sh.
         loss_scale: None | float (initial scale) | amp.LossScaler | amp.DeviceLossScaler -- fp16 training under the
         f16 library, which refuses to train without one; the bf16 library takes none.  use_8bit_adam: the script's
         --use_8bit_adam (DB:630), the blockwise 8-bit AdamW as in PSOTrainer.  optimizer: "adamw" or "prodigy"
         (--optimizer, DB:622-627; case-insensitive) with the prodigy_* arguments of PSOTrainer; Prodigy wants a
-        learning_rate around 1.0 and reads betas, adam_weight_decay and adam_epsilon as the diffusers script does."""
+        learning_rate around 1.0 and reads betas, adam_weight_decay and adam_epsilon as the diffusers script does.
+        lr_scheduler / lr_warmup_steps / max_train_steps / lr_num_cycles / lr_power: the script's get_scheduler call
+        (DB:1614-1621), stepped once per applied optimizer step (DB:1962-1963); "constant" builds no schedule
+        (self.lr_schedule is None) whatever lr_warmup_steps says, as diffusers' constant kind ignores it."""
         if loss_type not in ("pso", "pso_db"):
             raise ValueError(f"Unknown loss type {loss_type}")  # DB:1929
         self.scaler = make_scaler(loss_scale)
@@ -73,6 +78,7 @@ class DreamBoothPSOTrainer:
                              prodigy_use_bias_correction=prodigy_use_bias_correction,
                              prodigy_safeguard_warmup=prodigy_safeguard_warmup, prodigy_d0=prodigy_d0,
                              prodigy_d_coef=prodigy_d_coef, prodigy_growth_rate=prodigy_growth_rate)
+        init_lr_schedule(self, lr_scheduler, lr_warmup_steps, max_train_steps, lr_num_cycles, lr_power)
         self.clip_buf = torch.zeros(2, device=st.master.device, dtype=torch.float32)
         self.opt_step = 0
         self.n_micro = 0
@@ -80,7 +86,8 @@ class DreamBoothPSOTrainer:
         self.auto_step = True
 
     @classmethod
-    def from_args(cls, unet, vae, args, process_group=None, loss_scale=None, allow_prodigy=False):
+    def from_args(cls, unet, vae, args, process_group=None, loss_scale=None, allow_prodigy=False,
+                  allow_lr_schedule=False):
         """Build from the reference script's argparse namespace (DB:parse_args).  Read: loss_type, beta_pso,
         neg_defactor, prior_loss_weight, distill_train_timesteps, learning_rate, adam_beta1 / adam_beta2 /
         adam_weight_decay / adam_epsilon, max_grad_norm, gradient_accumulation_steps, use_8bit_adam, mixed_precision,
@@ -88,7 +95,11 @@ class DreamBoothPSOTrainer:
         prodigy_beta3 / prodigy_decouple / prodigy_use_bias_correction / prodigy_safeguard_warmup (DB:641-673), which
         also warns for a learning_rate <= 0.1 and ignores use_8bit_adam with a warning (DB:1486-1490).  Prodigy
         trains with allow_prodigy=True only: without it optimizer="prodigy" raises ValueError as it always has, so a
-        caller that relied on the refusal keeps it;
+        caller that relied on the refusal keeps it.  The same holds for the learning-rate schedule: with
+        allow_lr_schedule=True lr_scheduler, lr_warmup_steps (script default 500), max_train_steps, lr_num_cycles and
+        lr_power are read and the schedule is built (DB:1614-1621; the script's own defaults -- "constant" with a
+        warm-up of 500 that the constant kind ignores -- give none); without it anything but "constant" with zero
+        warm-up raises ValueError as it always has;
         a field the namespace does not carry counts as the script's default.  Flags that ask for training this
         trainer does not implement raise ValueError naming the flag (unet.check_lora_config's rule) instead of
         training something else.
@@ -129,11 +140,17 @@ class DreamBoothPSOTrainer:
             raise ValueError("--do_edm_style_training is required: only the EDM-style epsilon training of the recipes "
                              "(DB:1787-1796) is implemented")
         sched = get("lr_scheduler", "constant")
-        if sched != "constant":
-            raise ValueError(f"--lr_scheduler={sched!r} is not implemented (constant only)")
-        if get("lr_warmup_steps", 500) != 0:
-            raise ValueError(f"--lr_warmup_steps={get('lr_warmup_steps', 500)!r} is not implemented: the constant "
-                             "schedule here has no warm-up (the recipes pass 0)")
+        schedule = {}
+        if allow_lr_schedule:
+            schedule = dict(lr_scheduler=sched, lr_warmup_steps=get("lr_warmup_steps", 500),
+                            max_train_steps=get("max_train_steps", None), lr_num_cycles=get("lr_num_cycles", 1),
+                            lr_power=get("lr_power", 1.0))
+        else:
+            if sched != "constant":
+                raise ValueError(f"--lr_scheduler={sched!r} is not implemented (constant only)")
+            if get("lr_warmup_steps", 500) != 0:
+                raise ValueError(f"--lr_warmup_steps={get('lr_warmup_steps', 500)!r} is not implemented: the constant "
+                                 "schedule here has no warm-up (the recipes pass 0)")
         mp = get("mixed_precision", None)
         if _lib.ELEM_DTYPE == torch.float16:
             if mp != "fp16":
@@ -151,7 +168,7 @@ class DreamBoothPSOTrainer:
                    adam_weight_decay=get("adam_weight_decay", 1e-4), adam_epsilon=get("adam_epsilon", 1e-8),
                    max_grad_norm=get("max_grad_norm", 1.0),
                    gradient_accumulation_steps=get("gradient_accumulation_steps", 1), process_group=process_group,
-                   loss_scale=loss_scale, use_8bit_adam=use_8bit_adam, optimizer=optimizer, **prodigy)
+                   loss_scale=loss_scale, use_8bit_adam=use_8bit_adam, optimizer=optimizer, **prodigy, **schedule)
 
     @property
     def loss_scale(self):

@@ -1088,10 +1088,39 @@ def amp_update(amp_state, growth_factor, backoff_factor, growth_interval):
                                stream_ptr()), "pso_amp_update")
 
 
+def _check_lr_word(lr_word):
+    require_cuda(lr_word)
+    if lr_word.dtype != torch.float32 or lr_word.numel() != 1:
+        raise _lib.PsoLibError("the device learning rate must be a one-element float32 device tensor")
+    return lr_word
+
+
+def lr_schedule(sched, out, step=None, amp_state=None):
+    """out[0] (one float32 on the device) = float32(sched.lr(k)), evaluated on the device (pso_lr_schedule; sched =
+    lr_schedule.LrSchedule).  k = step - 1 from the host, or -- amp_state: an amp.DeviceLossScaler's state, after
+    amp_unscale_clip -- its applied-step word - 1, with `out` left as it is on a skipped step.  No read-back."""
+    _check_lr_word(out)
+    if amp_state is not None:
+        _check_amp_state(amp_state)
+    elif step is None:
+        raise _lib.PsoLibError("lr_schedule needs step (counting from 1) or amp_state")
+    total = 0 if sched.num_training_steps is None else sched.num_training_steps
+    check(lib().pso_lr_schedule(sched.kind_code, float(sched.base_lr), int(sched.num_warmup_steps), int(total),
+                                int(sched.num_cycles), float(sched.power), ptr(amp_state),
+                                0 if step is None else int(step), ptr(out), stream_ptr()), "pso_lr_schedule")
+    return out
+
+
 def adamw_step_amp(param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, amp_state):
-    """adamw_step with the gradient factor, the step's bias corrections and the inf-skip read from the state."""
+    """adamw_step with the gradient factor, the step's bias corrections and the inf-skip read from the state.  lr: a
+    Python float, or a one-element float32 device tensor (pso_adamw_step_amp_lr reads the step's lr there)."""
     require_cuda(param, grad, exp_avg, exp_avg_sq)
     _check_amp_state(amp_state)
+    if torch.is_tensor(lr):
+        check(lib().pso_adamw_step_amp_lr(param.numel(), ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq),
+                                          ptr(_check_lr_word(lr)), float(betas[0]), float(betas[1]), float(eps),
+                                          float(weight_decay), ptr(amp_state), stream_ptr()), "pso_adamw_step_amp_lr")
+        return
     check(lib().pso_adamw_step_amp(param.numel(), ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), float(lr),
                                    float(betas[0]), float(betas[1]), float(eps), float(weight_decay), ptr(amp_state),
                                    stream_ptr()), "pso_adamw_step_amp")
@@ -1099,7 +1128,8 @@ def adamw_step_amp(param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_deca
 
 def adamw8bit_step_amp(param, grad, state, lr, betas, eps, weight_decay, amp_state, out_bf16=None, zero_grad=False):
     """adamw8bit_step (per-tensor block tables only) driven by the loss-scaler state; returns whether the gradient
-    was zeroed -- it is on a skipped step too."""
+    was zeroed -- it is on a skipped step too.  lr: a Python float, or a one-element float32 device tensor (the word
+    lr_schedule wrote) for the `_lr` entries, which read the step's lr on the device."""
     require_cuda(param, grad)
     _check_amp_state(amp_state)
     if state.desc is None:
@@ -1107,9 +1137,13 @@ def adamw8bit_step_amp(param, grad, state, lr, betas, eps, weight_decay, amp_sta
     if out_bf16 is not None:
         assert out_bf16.dtype == ELEM and out_bf16.numel() == param.numel() and out_bf16.is_contiguous()
     fn = "pso_adamw8bit_step_blocks_zero_grad_amp" if zero_grad else "pso_adamw8bit_step_blocks_amp"
+    if torch.is_tensor(lr):
+        fn, lr = fn + "_lr", ptr(_check_lr_word(lr))
+    else:
+        lr = float(lr)
     check(getattr(lib(), fn)(param.numel(), state.nblk, ptr(state.desc), ptr(param), ptr(out_bf16), ptr(grad),
                              ptr(state.qm), ptr(state.qv), ptr(state.am), ptr(state.av), ptr(state.m32),
-                             ptr(state.v32), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                             ptr(state.v32), lr, float(betas[0]), float(betas[1]), float(eps),
                              float(weight_decay), ptr(amp_state), stream_ptr()), fn)
     return zero_grad
 
@@ -1155,7 +1189,8 @@ def prodigy_step(param, grad, state, lr, betas, eps, weight_decay, beta3=None, d
     """One Prodigy step on the flat fp32 param with state = ProdigyState: three launches, nothing read back (k, d and
     dlr live in the state block).  beta3 None = sqrt(beta2), prodigyopt's default.  amp_state: an
     amp.DeviceLossScaler's state -- the gradient factor and the inf-skip come from it and grad_scale / clip are not
-    read."""
+    read.  lr: a Python float (> 0), or a one-element float32 device tensor (pso_prodigy_step_lr reads the step's lr
+    there; 0 is legal)."""
     require_cuda(param, grad)
     if amp_state is not None:
         _check_amp_state(amp_state)
@@ -1171,11 +1206,15 @@ def prodigy_step(param, grad, state, lr, betas, eps, weight_decay, beta3=None, d
     flags = ((_lib.PRODIGY_DECOUPLE if decouple else 0) | (_lib.PRODIGY_BIAS_CORRECTION if use_bias_correction else 0)
              | (_lib.PRODIGY_SAFEGUARD_WARMUP if safeguard_warmup else 0))
     beta3 = math.sqrt(float(betas[1])) if beta3 is None else float(beta3)
-    check(lib().pso_prodigy_step(n, ptr(param), ptr(grad), ptr(state.p0), ptr(state.exp_avg), ptr(state.exp_avg_sq),
-                                 ptr(state.s), ptr(state.state), float(lr), float(betas[0]), float(betas[1]), beta3,
-                                 float(eps), float(weight_decay), flags, float(d_coef), float(growth_rate),
-                                 float(grad_scale), ptr(clip), ptr(amp_state), ptr(state.ws), state.ws.numel(),
-                                 stream_ptr()), "pso_prodigy_step")
+    if torch.is_tensor(lr):
+        fn, lr = "pso_prodigy_step_lr", ptr(_check_lr_word(lr))
+    else:
+        fn, lr = "pso_prodigy_step", float(lr)
+    check(getattr(lib(), fn)(n, ptr(param), ptr(grad), ptr(state.p0), ptr(state.exp_avg), ptr(state.exp_avg_sq),
+                             ptr(state.s), ptr(state.state), lr, float(betas[0]), float(betas[1]), beta3,
+                             float(eps), float(weight_decay), flags, float(d_coef), float(growth_rate),
+                             float(grad_scale), ptr(clip), ptr(amp_state), ptr(state.ws), state.ws.numel(),
+                             stream_ptr()), fn)
 
 
 def zero_(x):

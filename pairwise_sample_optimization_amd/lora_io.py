@@ -14,7 +14,10 @@
   additive key `loss_scaler` of `pso_state.json`; a checkpoint without it loads as before and keeps the trainer's
   scaler as constructed.  A Prodigy trainer (`optimizer="prodigy"`) writes `p0`, `exp_avg`, `exp_avg_sq`, `s` and
   the scalar state block `prodigy_state` instead, and `pso_state.json` names the optimizer under the additive key
-  `optimizer`; loading a checkpoint of the other optimizer raises `KeyError`.
+  `optimizer`; loading a checkpoint of the other optimizer raises `KeyError`.  A trainer with a learning-rate schedule
+  writes its `state_dict()` under the additive key `lr_schedule`; the position in the schedule is `opt_step` and needs
+  no field of its own.  On load the trainer's own schedule wins: one that differs from the checkpoint's (or a
+  checkpoint with a schedule into a trainer without) warns; a checkpoint without the key loads as before.
 """
 import json
 import os
@@ -96,6 +99,9 @@ def save_state(trainer, output_dir):
         scaler = getattr(trainer, "scaler", None)
         if scaler is not None:
             meta["loss_scaler"] = scaler.state_dict()
+        sched = getattr(trainer, "lr_schedule", None)
+        if sched is not None:
+            meta["lr_schedule"] = sched.state_dict()
         json.dump(meta, f)
 
 
@@ -145,3 +151,13 @@ def load_state(trainer, input_dir):
     if scaler is not None and "loss_scaler" in meta:
         scaler.load_state_dict(meta["loss_scaler"])
     trainer.opt_step, trainer.n_micro = int(meta["opt_step"]), int(meta["n_micro"])
+    if "lr_schedule" in meta:
+        sched = getattr(trainer, "lr_schedule", None)
+        mine = None if sched is None else sched.state_dict()
+        if mine != meta["lr_schedule"]:
+            warnings.warn(f"checkpoint was written with the learning-rate schedule {meta['lr_schedule']}, this trainer "
+                          f"runs {mine if mine is not None else 'a constant rate'}: the trainer's is kept, continuing "
+                          f"at optimizer step {trainer.opt_step}")
+    if getattr(trainer, "lr_word", None) is not None:  # last_lr reads the word: the resumed step's lr
+        from .trainer import sync_lr_word
+        sync_lr_word(trainer)

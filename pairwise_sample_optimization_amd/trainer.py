@@ -28,6 +28,7 @@ from . import _lib
 from . import kernels as K
 from . import pso_core
 from .amp import DeviceLossScaler, LossScaler, make_scaler
+from .lr_schedule import make_lr_schedule
 from ._lib import MODE_TURBO, MODE_DMD
 from .schedulers import EulerAncestralDiscreteScheduler, LCMScheduler, dmd_distill_timesteps
 
@@ -280,6 +281,50 @@ PRODIGY_KEYS = ("prodigy_beta3", "prodigy_decouple", "prodigy_use_bias_correctio
                 "prodigy_d0", "prodigy_d_coef", "prodigy_growth_rate")
 
 
+# the schedule arguments both trainers take (train.lr_* / train.max_train_steps of a run config, --lr_scheduler,
+# --lr_warmup_steps, --max_train_steps, --lr_num_cycles, --lr_power of the DreamBooth script, DB:586-612)
+LR_SCHEDULE_KEYS = ("lr_scheduler", "lr_warmup_steps", "max_train_steps", "lr_num_cycles", "lr_power")
+
+
+def init_lr_schedule(tr, lr_scheduler="constant", lr_warmup_steps=0, max_train_steps=None, lr_num_cycles=1,
+                     lr_power=1.0):
+    """tr.lr_schedule: None for "constant" -- the optimizer step then runs the fixed-rate code unchanged -- else the
+    lr_schedule.LrSchedule over tr.lr (which stays the base rate), stepped once per applied optimizer step
+    (DB:1614-1621, 1962-1963), and tr.lr_word, the one-float device tensor the optimizer kernels read the step's lr
+    from where the host cannot know it (amp.DeviceLossScaler: the applied-step count is on the device) or may not
+    pass it (Prodigy's host-argument entry rejects the 0 every warm-up starts at)."""
+    tr.lr_schedule = make_lr_schedule(lr_scheduler, tr.lr, lr_warmup_steps, max_train_steps, lr_num_cycles, lr_power)
+    tr.lr_word = None
+    if tr.lr_schedule is not None:
+        tr.lr_word = torch.zeros(1, device=trainable(tr.unet)[0].device, dtype=torch.float32)
+
+
+def sync_lr_word(tr):
+    """After opt_step was set from outside (a checkpoint): the lr word holds the last applied step's lr again."""
+    sched = getattr(tr, "lr_schedule", None)
+    if sched is not None and getattr(tr, "lr_word", None) is not None:
+        k = tr.opt_step
+        tr.lr_word.fill_(sched.lr32(k - 1) if k >= 1 else 0.0)
+
+
+class LastLr:
+    """trainer.last_lr: the learning rate of the last applied optimizer step as the kernels saw it (float32), None
+    before the first.  Without a schedule it is trainer.lr; with an amp.DeviceLossScaler it reads the device word --
+    a sync, by request only, like the scaler's `.scale`."""
+
+    def __get__(self, tr, owner=None):
+        if tr is None:
+            return self
+        if tr.opt_step < 1:
+            return None
+        sched = getattr(tr, "lr_schedule", None)
+        if sched is None:
+            return float(tr.lr)
+        if isinstance(getattr(tr, "scaler", None), DeviceLossScaler):
+            return float(tr.lr_word.item())
+        return sched.lr32(tr.opt_step - 1)
+
+
 def normalize_optimizer(name):
     """'adamw' or 'prodigy' (case-insensitive, the DreamBooth script's --optimizer, DB:622-627)."""
     opt = str(name).lower()
@@ -324,18 +369,23 @@ def _amp_optimizer_step(tr, scaler, scale):
     master, grad, refresh = trainable(tr.unet)
     st = scaler.state
     K.amp_unscale_clip(grad, tr.max_grad_norm, st, tr.betas, grad_scale=scale)
+    # a schedule: the step's lr is evaluated on the device from the state's applied-step count (a skipped step leaves
+    # the word as it was) and the `_lr` entries read it there; without one the host float goes in as it always has
+    lr = tr.lr
+    if getattr(tr, "lr_schedule", None) is not None:
+        lr = K.lr_schedule(tr.lr_schedule, tr.lr_word, amp_state=st)
     cast = True
     if getattr(tr, "prodigy", None) is not None:
         zeroed = False
-        K.prodigy_step(master, grad, tr.prodigy, tr.lr, tr.betas, tr.adam_eps, tr.wd, amp_state=st, **tr.prodigy_opts)
+        K.prodigy_step(master, grad, tr.prodigy, lr, tr.betas, tr.adam_eps, tr.wd, amp_state=st, **tr.prodigy_opts)
     elif getattr(tr, "adam8", None) is not None:
         work = _work_copy(tr.unet, master)
-        zeroed = K.adamw8bit_step_amp(master, grad, tr.adam8, tr.lr, tr.betas, tr.adam_eps, tr.wd, st, out_bf16=work,
+        zeroed = K.adamw8bit_step_amp(master, grad, tr.adam8, lr, tr.betas, tr.adam_eps, tr.wd, st, out_bf16=work,
                                       zero_grad=True)
         cast = work is None
     else:
         zeroed = False
-        K.adamw_step_amp(master, grad, tr.exp_avg, tr.exp_avg_sq, tr.lr, tr.betas, tr.adam_eps, tr.wd, st)
+        K.adamw_step_amp(master, grad, tr.exp_avg, tr.exp_avg_sq, lr, tr.betas, tr.adam_eps, tr.wd, st)
     K.amp_update(st, scaler.growth_factor, scaler.backoff_factor, scaler.growth_interval)
     if not zeroed:
         K.zero_(grad)
@@ -348,7 +398,8 @@ def lora_optimizer_step(tr):
     folded into the gradient read) -> zero -> refresh the bf16 working copies.  tr carries exp_avg, exp_avg_sq,
     opt_step, clip_buf, lr, betas, adam_eps, wd, max_grad_norm, pg and, when the last backward of the window already
     issued the bucketed all-reduce (tr.sync_armed), the GradBuckets to finish.  fp16 training: tr.scaler is an
-    amp.LossScaler (the norm is read back, one sync) or an amp.DeviceLossScaler (_amp_optimizer_step: no read-back)."""
+    amp.LossScaler (the norm is read back, one sync) or an amp.DeviceLossScaler (_amp_optimizer_step: no read-back).
+    tr.lr_schedule (None = the fixed rate tr.lr): the step runs at lr_schedule.lr(k), k = the steps applied before it."""
     master, grad, refresh = trainable(tr.unet)
     if getattr(tr, "sync_armed", False):
         scale = tr.buckets.finish()
@@ -372,21 +423,28 @@ def lora_optimizer_step(tr):
             K.zero_(grad)
             return
     tr.opt_step += 1
+    # a schedule (DB:1614-1621, stepped at DB:1962-1963): this step runs at lr(opt_step - 1) -- the host knows the
+    # count here, so AdamW takes the value as the float it always took; Prodigy's host-argument entry rejects the 0 a
+    # warm-up starts at, so its lr goes through the device word (one single-lane launch)
+    sched = getattr(tr, "lr_schedule", None)
+    lr = tr.lr if sched is None else sched.lr(tr.opt_step - 1)
     cast = True
     if getattr(tr, "prodigy", None) is not None:  # optimizer="prodigy": k, d and dlr stay on the device
         zeroed = False
-        K.prodigy_step(master, grad, tr.prodigy, tr.lr, tr.betas, tr.adam_eps, tr.wd, grad_scale=scale,
+        if sched is not None:
+            lr = K.lr_schedule(sched, tr.lr_word, step=tr.opt_step)
+        K.prodigy_step(master, grad, tr.prodigy, lr, tr.betas, tr.adam_eps, tr.wd, grad_scale=scale,
                        clip=tr.clip_buf, **tr.prodigy_opts)
     elif getattr(tr, "adam8", None) is not None:  # train.use_8bit_adam: bitsandbytes AdamW8bit (T:427-435)
         work = _work_copy(tr.unet, master)  # the step also writes the bf16 working copy (no separate cast pass)
         # with a per-tensor block table the step also zeroes the gradient it reads (the pads between tensors are
         # zero from allocation and no kernel writes them)
-        zeroed = K.adamw8bit_step(master, grad, tr.adam8, tr.lr, tr.betas, tr.adam_eps, tr.wd, tr.opt_step,
+        zeroed = K.adamw8bit_step(master, grad, tr.adam8, lr, tr.betas, tr.adam_eps, tr.wd, tr.opt_step,
                                   grad_scale=scale, clip=tr.clip_buf, out_bf16=work, zero_grad=True)
         cast = work is None
     else:
         zeroed = False
-        K.adamw_step(master, grad, tr.exp_avg, tr.exp_avg_sq, tr.lr, tr.betas, tr.adam_eps, tr.wd, tr.opt_step,
+        K.adamw_step(master, grad, tr.exp_avg, tr.exp_avg_sq, lr, tr.betas, tr.adam_eps, tr.wd, tr.opt_step,
                      grad_scale=scale, clip=tr.clip_buf)
     if not zeroed:
         K.zero_(grad)
@@ -395,6 +453,7 @@ def lora_optimizer_step(tr):
 
 class PSOTrainer:
     opt_step = OptStep()
+    last_lr = LastLr()
 
     def __init__(self, unet, mode="turbo", num_steps=2, beta=50.0, clip_eps=0.1, lr=1e-5, betas=(0.9, 0.999),
                  weight_decay=1e-6, adam_eps=1e-8, max_grad_norm=1.0, gradient_accumulation_steps=1,
@@ -402,7 +461,8 @@ class PSOTrainer:
                  latent_dtype=torch.float32, allreduce_dtype=None, use_8bit_adam=False, overlap_sync=None,
                  bucket_mb=32.0, loss_scale=None, optimizer="adamw", prodigy_beta3=None, prodigy_decouple=True,
                  prodigy_use_bias_correction=False, prodigy_safeguard_warmup=False, prodigy_d0=1e-6,
-                 prodigy_d_coef=1.0, prodigy_growth_rate=float("inf")):
+                 prodigy_d_coef=1.0, prodigy_growth_rate=float("inf"), lr_scheduler="constant", lr_warmup_steps=0,
+                 max_train_steps=None, lr_num_cycles=1, lr_power=1.0):
         self.unet = unet
         # loss_scale: None (no scaling), a float (initial scale), an amp.LossScaler or an amp.DeviceLossScaler (state
         # on the device, no sync in the optimizer step): dynamic loss scaling with inf-skip for fp16 training.
@@ -436,6 +496,9 @@ class PSOTrainer:
                              prodigy_use_bias_correction=prodigy_use_bias_correction,
                              prodigy_safeguard_warmup=prodigy_safeguard_warmup, prodigy_d0=prodigy_d0,
                              prodigy_d_coef=prodigy_d_coef, prodigy_growth_rate=prodigy_growth_rate)
+        # lr_scheduler / lr_warmup_steps / max_train_steps / lr_num_cycles / lr_power: diffusers' get_scheduler names
+        # (DB:586-612); "constant" (the default) builds no schedule and the optimizer step is the fixed-rate one
+        init_lr_schedule(self, lr_scheduler, lr_warmup_steps, max_train_steps, lr_num_cycles, lr_power)
         self.opt_step = 0
         self.n_micro = 0
         self.clip_buf = torch.zeros(2, device=master.device, dtype=torch.float32)
@@ -494,7 +557,9 @@ class PSOTrainer:
         that dtype; pass torch.float32 to train on the fp32 step math instead.  A value that disagrees with the
         config is honoured with a warning.
         loss_scale (f16 library only): the scaler to train with instead of the default host amp.LossScaler(), e.g.
-        an amp.DeviceLossScaler."""
+        an amp.DeviceLossScaler.
+        train.{lr_scheduler, lr_warmup_steps, max_train_steps, lr_num_cycles, lr_power} are read when present (the
+        reference configs carry none: an absent lr_scheduler is "constant")."""
         tr = config.train
         if tr.distilled_train_steps != config.sample.num_steps - 1:
             raise AssertionError("train.distilled_train_steps must equal sample.num_steps - 1 "
@@ -522,7 +587,7 @@ class PSOTrainer:
                    num_reward=num_reward, process_group=process_group, ref_unet=ref_unet, latent_dtype=latent_dtype,
                    use_8bit_adam=bool(getattr(tr, "use_8bit_adam", False)), loss_scale=loss_scale,
                    optimizer=getattr(tr, "optimizer", "adamw"),
-                   **{k: getattr(tr, k) for k in PRODIGY_KEYS if hasattr(tr, k)})
+                   **{k: getattr(tr, k) for k in PRODIGY_KEYS + LR_SCHEDULE_KEYS if hasattr(tr, k)})
 
     # ------------------------------------------------------------------------------------------------------------
     # coefficients of transition j (host float32 scalars, the reference's operation order)
