@@ -306,7 +306,9 @@ int pso_group_norm_bwd(int B, int HW, int C, int G, const void* x, const void* d
                        float* dbeta, int accumulate_dparams, void* ws, size_t ws_bytes, void* stream);
 
 /* LayerNorm over the last dim (C <= 2048), bf16 I/O, stats [M][2] fp32.
- * Replaces: torch.nn.LayerNorm norm1/norm2/norm3 of diffusers BasicTransformerBlock (and its backward). */
+ * Replaces: torch.nn.LayerNorm norm1/norm2/norm3 of diffusers BasicTransformerBlock (and its backward).
+ * Rows are read and written 16 bytes at a time: every base pointer (gamma, beta, dadd included) must be 16-byte
+ * aligned and every ld a multiple of 8 elements, else PSO_ERR_ARG before any launch. */
 int pso_layer_norm_fwd(int M, int C, float eps, const void* x, long ldx, const void* gamma, const void* beta, void* y,
                        long ldy, float* stats, void* stream);
 int pso_layer_norm_bwd(int M, int C, const void* x, long ldx, const void* dy, long lddy, const float* stats,

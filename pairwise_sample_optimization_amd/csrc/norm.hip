@@ -416,6 +416,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(int M, int C, const bf16_t*
   }
 }
 
+static bool ln_aligned16(const void* p, long ld) { return (((uintptr_t)p) & 15) == 0 && (ld % 8) == 0; }
+
 extern "C" {
 
 size_t pso_group_norm_ws_bytes(int B, int HW, int C) {
@@ -498,6 +500,9 @@ int pso_layer_norm_fwd(int M, int C, float eps, const void* x, long ldx, const v
                        long ldy, float* stats, void* stream) {
   PSO_ARG_CHECK(M >= 0 && C > 0 && C % 8 == 0 && C <= 64 * 8 * 4, "pso_layer_norm_fwd: C=%d unsupported", C);
   PSO_ARG_CHECK(x && y && gamma && beta, "pso_layer_norm_fwd: null pointer");
+  // every row of every operand is read or written 16 bytes at a time
+  PSO_ARG_CHECK(ln_aligned16(x, ldx) && ln_aligned16(y, ldy) && ln_aligned16(gamma, 0) && ln_aligned16(beta, 0),
+                "pso_layer_norm_fwd: x, y, gamma, beta need 16-B aligned rows (pointers, and ld % 8 == 0)");
   if (M == 0) return PSO_OK;
   hipStream_t st = (hipStream_t)stream;
   const int C8 = C / 8;
@@ -518,6 +523,9 @@ int pso_layer_norm_bwd(int M, int C, const void* x, long ldx, const void* dy, lo
                        const void* gamma, const void* dadd, long ldadd, void* dx, long lddx, void* stream) {
   PSO_ARG_CHECK(M >= 0 && C > 0 && C % 8 == 0 && C <= 64 * 8 * 4, "pso_layer_norm_bwd: C=%d unsupported", C);
   PSO_ARG_CHECK(x && dy && stats && gamma && dx, "pso_layer_norm_bwd: null pointer");
+  PSO_ARG_CHECK(ln_aligned16(x, ldx) && ln_aligned16(dy, lddy) && ln_aligned16(gamma, 0) && ln_aligned16(dx, lddx) &&
+                    (!dadd || ln_aligned16(dadd, ldadd)),
+                "pso_layer_norm_bwd: x, dy, gamma, dadd, dx need 16-B aligned rows (pointers, and ld % 8 == 0)");
   if (M == 0) return PSO_OK;
   hipStream_t st = (hipStream_t)stream;
   const int C8 = C / 8;

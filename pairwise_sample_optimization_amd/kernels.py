@@ -548,11 +548,24 @@ def db_loss_bwd(loss_type, eps, noisy, x0, sigma, beta, neg_defactor, prior_w, w
 # ------------------------------------------------------------------------------------------------------------------
 # Norms
 # ------------------------------------------------------------------------------------------------------------------
-def group_norm_fwd(x, gamma, beta, groups, eps, silu):
-    """x NHWC [B,H,W,C] (or [B,HW,C]) bf16 -> (y, stats[B,G,2])."""
+def _norm_out(out, like, rows_contiguous):
+    """The optional out= of the norm wrappers: a fresh tensor when omitted, else the caller's view (same shape and
+    dtype; contiguous for GroupNorm, any 2-D row-strided view for LayerNorm)."""
+    if out is None:
+        if rows_contiguous:
+            return torch.empty_like(like)
+        return torch.empty(like.shape, device=like.device, dtype=like.dtype)
+    require_cuda(out)
+    assert out.shape == like.shape and out.dtype == like.dtype, (out.shape, out.dtype, like.shape, like.dtype)
+    assert not rows_contiguous or out.is_contiguous(), "GroupNorm writes contiguous NHWC rows"
+    return out
+
+
+def group_norm_fwd(x, gamma, beta, groups, eps, silu, out=None):
+    """x NHWC [B,H,W,C] (or [B,HW,C]) bf16 -> (y, stats[B,G,2]).  out: a contiguous tensor of x's shape to write y to."""
     B, C = x.shape[0], x.shape[-1]
     HW = x.numel() // (B * C)
-    y = torch.empty_like(x)
+    y = _norm_out(out, x, True)
     stats = torch.empty((B, groups, 2), device=x.device, dtype=torch.float32)
     wsb = lib().pso_group_norm_ws_bytes(B, HW, C)
     ws = torch.empty(wsb, device=x.device, dtype=torch.uint8)
@@ -561,11 +574,12 @@ def group_norm_fwd(x, gamma, beta, groups, eps, silu):
     return y, stats
 
 
-def group_norm_bwd(x, dy, stats, gamma, beta, silu, dadd=None, dgamma=None, dbeta=None, accumulate=False):
+def group_norm_bwd(x, dy, stats, gamma, beta, silu, dadd=None, dgamma=None, dbeta=None, accumulate=False, out=None):
+    """out: a contiguous tensor of x's shape to write dx to."""
     B, C = x.shape[0], x.shape[-1]
     G = stats.shape[1]
     HW = x.numel() // (B * C)
-    dx = torch.empty_like(x)
+    dx = _norm_out(out, x, True)
     wsb = lib().pso_group_norm_ws_bytes(B, HW, C)
     ws = torch.empty(wsb, device=x.device, dtype=torch.uint8)
     check(lib().pso_group_norm_bwd(B, HW, C, G, ptr(x), ptr(dy.contiguous()), ptr(stats), ptr(gamma), ptr(beta),
@@ -574,21 +588,22 @@ def group_norm_bwd(x, dy, stats, gamma, beta, silu, dadd=None, dgamma=None, dbet
     return dx
 
 
-def layer_norm_fwd(x, gamma, beta, eps):
-    """x [M, C] (row-strided view ok) -> (y [M,C], stats [M,2])."""
+def layer_norm_fwd(x, gamma, beta, eps, out=None):
+    """x [M, C] (row-strided view ok) -> (y [M,C], stats [M,2]).  out: a [M, C] view (row-strided ok) to write y to."""
     M, C = x.shape
-    y = torch.empty((M, C), device=x.device, dtype=x.dtype)
+    y = _norm_out(out, x, False)
     stats = torch.empty((M, 2), device=x.device, dtype=torch.float32)
-    check(lib().pso_layer_norm_fwd(M, C, float(eps), ptr(x), _row_stride(x), ptr(gamma), ptr(beta), ptr(y), C,
-                                   ptr(stats), stream_ptr()), "pso_layer_norm_fwd")
+    check(lib().pso_layer_norm_fwd(M, C, float(eps), ptr(x), _row_stride(x), ptr(gamma), ptr(beta), ptr(y),
+                                   _row_stride(y), ptr(stats), stream_ptr()), "pso_layer_norm_fwd")
     return y, stats
 
 
-def layer_norm_bwd(x, dy, stats, gamma, dadd=None):
+def layer_norm_bwd(x, dy, stats, gamma, dadd=None, out=None):
+    """out: a [M, C] view (row-strided ok) to write dx to."""
     M, C = x.shape
-    dx = torch.empty((M, C), device=x.device, dtype=x.dtype)
+    dx = _norm_out(out, x, False)
     check(lib().pso_layer_norm_bwd(M, C, ptr(x), _row_stride(x), ptr(dy), _row_stride(dy), ptr(stats), ptr(gamma),
-                                   ptr(dadd), _row_stride(dadd) if dadd is not None else 0, ptr(dx), C,
+                                   ptr(dadd), _row_stride(dadd) if dadd is not None else 0, ptr(dx), _row_stride(dx),
                                    stream_ptr()), "pso_layer_norm_bwd")
     return dx
 

@@ -9,6 +9,8 @@ contiguous output tensor cannot show a store that lands beside the slice it was 
   attention_model  the attention kernels' documented roundings restated in plain torch (sets the per-row bound)
   attention_fp64   the reference
   geglu_* / gemm_* cases, fp64 references and derived element-wise bounds of the GEMM epilogue tests
+  group_norm_* / layer_norm_* / norm_*  fp64 references, rounding models, edge-weighted inputs and derived bounds of
+                   the norm kernels, saved statistics and parameter gradients included
 
 Everything here runs on whatever device its inputs are on; tests/test_parity_util.py exercises it without a GPU.
 """
@@ -499,3 +501,612 @@ def gemm_restatement(inp, group, tail_rows, mode):
     if "resid" in inp:
         y = (y.float() + inp["resid"].float()).bfloat16()
     return y
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# GroupNorm / LayerNorm (norm.hip) and the ordered LayerNorm parameter gradients (pso_layer_norm_dparam_ws)
+# ----------------------------------------------------------------------------------------------------------------------
+# What the norm tests hold a kernel to, all of it from the reference side:
+#   saved statistics  |mean - mean64| <= F 2^-23 mean|x|  and  |rstd / rstd64 - 1| <= F 2^-23 (E[x^2] + eps) / (var + eps)
+#                     per group / row.  (E[x^2] + eps) / (var + eps) is the cancellation amplification of the two-moment
+#                     form var = E[x^2] - mean^2: ~1 for centred data, ~1000 at mean / std = 32.
+#   y, dx             rowwise_rel(got, ref64, 8) -- one 16-byte store chunk, the unit every norm kernel writes --
+#                     within ROW_BOUND_FACTOR x the worst chunk of the rounding model on the same inputs
+#   dgamma, dbeta     element-wise F2 2^-23 sum|dz xhat| and F2 2^-23 sum|dz| (+ 2^-23 |previous contents|)
+NORM_EPS = 1e-5
+GN_ROWS, GN_ROWS_BIG = 64, 512   # pixel rows per block; the forward's above 256 blocks per image (norm.hip)
+LN_DPARAM_ROWS = 64              # CS2_ROWS of fullgrad.hip
+EDGE_SCALE = 32.0
+ELEM_ULP = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}
+
+# F and F2 are NOT taken from a kernel run: tests/test_parity_util.py restates the sums in fp32 with the kernels' own
+# sequential chain lengths (gn_partial_kernel: a thread's pixel rows, then the RS row slots, then the Cg channels of a
+# group; ln_*_kernel: a lane's 8 * MAXV channels, then the 64-lane butterfly; the dparam kernels: a thread's rows, the
+# row slices, the ordered levels), takes the worst error over every named case in bf16 and fp16 in units of the
+# expressions above, and checks that each constant is 4 x that worst, rounded up to a power of two and no smaller than
+# 8.  Measured worst ratios (CPU restatement):
+#   statistics       mean 0.495 units, rstd 2.393 units                       -> F  = 16
+#   dgamma / dbeta   377.4 units over all named cases (the shifted GN case)   -> F2 = 2048
+#                    9.36 units over all of them but the shifted one          -> F2 (centred) = 64
+# Why two F2: xhat is proportional to rstd, so the error the statistics bound ALLOWS rstd -- F x the amplification,
+# ~1000 units at mean / std = 32 -- goes straight into dgamma; only the shifted case has it.  NORM_F2 is what the rule
+# gives over all named cases and is what the shifted case is held to; every other case is held to NORM_F2_CENTRED, the
+# same rule without that case, which implies NORM_F2.  (9 units, not 1: silu'(z) = sg (1 + z (1 - sg)) loses
+# |z| 2^-24 in 1 - sg, and the edge rows reach |z| ~ 15.)
+NORM_F = 16.0
+NORM_F2 = 2048.0
+NORM_F2_CENTRED = 64.0
+
+# (B, HW, C, G)
+GN_CASES = [
+    (2, 100, 320, 32),     # Cg = 10 straddles the 8-channel chunks; ragged second block of 36 rows
+    (1, 130, 1920, 32),    # SDXL's concatenated width, a 480-thread block, three blocks
+    (2, 70, 960, 32),      # the other concatenated width, 480 threads
+    (2, 70, 32, 32),       # Cg = 1
+    (2, 70, 64, 1),        # Cg = C
+    (1, 65, 8, 1),         # one thread per pixel row, 512 row slots
+    (1, 65, 4096, 32),     # the C limit: one row slot, 512 threads
+    (1, 70, 264, 33),      # a 264-thread block: no multiple of 64
+    (1, 16384, 32, 32),    # 256 blocks of 64 rows: the last size on GN_ROWS in the forward
+    (1, 16500, 128, 32),   # the GN_ROWS_BIG forward, ragged last block of 116 rows (the backward stays on 64)
+]
+GN_SHIFTED_CASE = (2, 100, 320, 32)   # x = 8 + 0.25 randn: the amplification term of the rstd bound at ~1000
+GN_NOAFFINE_CASE = (2, 100, 320, 32)  # gamma = beta = None
+# dgamma / dbeta reduction regimes of pso_group_norm_bwd at C = 64: BK = B * HW / 64 row blocks, S = BK >= 64 ? 32 :
+# BK / 2 splits, the single pass below S = 2.  (B, HW) -> BK = 1, 3 (single pass), 4, 5 (2 splits, ragged), 63 (31
+# splits, ragged), 64 (32 splits)
+GN_DPARAM_CASES = [(1, 64), (3, 64), (2, 128), (5, 64), (3, 1344), (2, 2048)]
+# (M, C): the MAXV 1 -> 2 -> 4 edges at C = 512 / 520 and 1024 / 1032, the smallest and the largest C, M < 4 (one
+# workgroup holds 4 rows), and more than one workgroup
+LN_CASES = [(5, 8), (3, 320), (7, 512), (7, 520), (6, 1024), (6, 1032), (9, 1280), (5, 2048), (1, 640), (2, 640),
+            (3, 640), (300, 640)]
+# (M, C, strided): one row; one row into a second block; the scalar tail (C % 8 != 0); 49 row blocks -> two-level
+# reduction, splits of 25 and 24; 66 row blocks -> splits of 22; row-strided x / dy
+LN_DPARAM_CASES = [(1, 640, False), (65, 640, False), (777, 12, False), (130, 100, False), (3100, 8, False),
+                   (4200, 320, False), (130, 640, True)]
+
+
+def _elem(dtype):
+    if dtype is None:
+        from pairwise_sample_optimization_amd import kernels as K
+        return K.ELEM
+    return dtype
+
+
+def _seed(*ns):
+    s = 12345
+    for n in ns:
+        s = (s * 1000003 + int(n)) % 2147483647
+    return s
+
+
+def gn_rows_fwd(HW):
+    return GN_ROWS_BIG if -(-HW // GN_ROWS) > 256 else GN_ROWS
+
+
+def gn_slots(C):
+    """RS of norm.hip's gn_block: row slots of a block of (C / 8) * RS <= 512 threads."""
+    tpr, rs = C // 8, 1
+    while tpr * rs * 2 <= 512:
+        rs *= 2
+    return rs
+
+
+def gn_edge_rows(HW):
+    """The pixel rows where a tiling mistake bites: first and last of the image, either side of the first 64-row block
+    boundary, and either side of the first 512-row one where the forward takes GN_ROWS_BIG."""
+    rows = {0, GN_ROWS - 1, GN_ROWS, HW - 1}
+    if gn_rows_fwd(HW) == GN_ROWS_BIG:
+        rows |= {GN_ROWS_BIG - 1, GN_ROWS_BIG}
+    return sorted(r for r in rows if 0 <= r < HW)
+
+
+def norm_inputs(kind, shape, dtype=None, device="cpu", shifted=False):
+    """x, dy, dadd, gamma, beta of one norm case in the element type, drawn on the CPU from a seed derived from the
+    shape (the CPU self-test and the GPU tests see the same numbers).  kind "gn": shape (B, HW, C, G), tensors
+    [B, HW, C]; kind "ln": shape (M, C), tensors [M, C].
+
+    Edge-weighted: the edge rows (gn_edge_rows; for LN the channels 0 and C - 1) are scaled by 32 in x and dy, so a
+    dropped, doubled or misattributed edge row moves its group's statistics and coefficients by tens of percent, not
+    by 1 / HW.  shifted: x = 8 + 0.25 randn with no edge weight on x (mean / std ~ 32 is the point of that case)."""
+    et = _elem(dtype)
+    g = torch.Generator().manual_seed(_seed(len(kind), int(shifted), *shape))
+    if kind == "gn":
+        B, HW, C, _ = shape
+        x, dy, dadd = (torch.randn(B, HW, C, generator=g) for _ in range(3))
+        rows = gn_edge_rows(HW)
+        dy[:, rows] *= EDGE_SCALE
+        if shifted:
+            x = 8.0 + 0.25 * x
+        else:
+            x[:, rows] *= EDGE_SCALE
+    else:
+        M, C = shape
+        x, dy, dadd = (torch.randn(M, C, generator=g) for _ in range(3))
+        x[:, [0, C - 1]] *= EDGE_SCALE
+        dy[:, [0, C - 1]] *= EDGE_SCALE
+    gamma = 1.0 + 0.25 * torch.randn(C, generator=g)
+    beta = 0.25 * torch.randn(C, generator=g)
+    return {k: v.to(et).to(device) for k, v in dict(x=x, dy=dy, dadd=dadd, gamma=gamma, beta=beta).items()}
+
+
+def _silu_parts(z):
+    sg = torch.sigmoid(z)
+    return z * sg, sg * (1 + z * (1 - sg))   # silu(z), silu'(z)
+
+
+def gn_reference(x, gamma, beta, G, eps, silu, dy=None, dadd=None):
+    """Everything the GroupNorm tests need from fp64, computed from the 16-bit inputs with nothing rounded: y, stats
+    [B, G, 2], dx, dgamma, dbeta, and the magnitudes the bounds are made of -- absx = mean|x|, ex2 = E[x^2], var per
+    group ([B, G]); mag_g = sum|dz xhat|, mag_b = sum|dz| per channel."""
+    B, HW, C = x.shape
+    Cg = C // G
+    xd = x.double().reshape(B, HW, G, Cg)
+    mean = xd.mean((1, 3), keepdim=True)
+    var = ((xd - mean) ** 2).mean((1, 3), keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    one = torch.ones(C, dtype=torch.float64, device=x.device)
+    gm = (gamma.double() if gamma is not None else one).reshape(1, 1, G, Cg)
+    bt = (beta.double() if beta is not None else 0 * one).reshape(1, 1, G, Cg)
+    xh = (xd - mean) * rstd
+    z = xh * gm + bt
+    r = dict(y=(_silu_parts(z)[0] if silu else z).reshape(B, HW, C),
+             stats=torch.stack([mean.reshape(B, G), rstd.reshape(B, G)], -1), eps=eps,
+             absx=xd.abs().mean((1, 3)), ex2=(xd * xd).mean((1, 3)), var=var.reshape(B, G),
+             dx=None, dgamma=None, dbeta=None)
+    if dy is not None:
+        dz = dy.double().reshape(B, HW, G, Cg)
+        if silu:
+            dz = dz * _silu_parts(z)[1]
+        gd = dz * gm
+        a = gd.mean((1, 3), keepdim=True)
+        b = (gd * xh).mean((1, 3), keepdim=True)
+        dx = (rstd * (gd - a - xh * b)).reshape(B, HW, C)
+        r.update(dx=dx + dadd.double() if dadd is not None else dx,
+                 dgamma=(dz * xh).sum((0, 1)).reshape(C), dbeta=dz.sum((0, 1)).reshape(C),
+                 mag_g=(dz * xh).abs().sum((0, 1)).reshape(C), mag_b=dz.abs().sum((0, 1)).reshape(C))
+    return r
+
+
+def group_norm_fp64(x, gamma, beta, G, eps, silu, dy=None, dadd=None):
+    """(y, stats[B, G, 2], dx, dgamma, dbeta) in fp64 (the last three None without dy); gamma / beta may be None."""
+    r = gn_reference(x, gamma, beta, G, eps, silu, dy, dadd)
+    return r["y"], r["stats"], r["dx"], r["dgamma"], r["dbeta"]
+
+
+def ln_reference(x, gamma, beta, eps, dy=None, dadd=None):
+    """gn_reference's LayerNorm twin: per-row statistics [M, 2]; dz = dy (no activation is fused)."""
+    xd = x.double()
+    mean = xd.mean(1, keepdim=True)
+    var = ((xd - mean) ** 2).mean(1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    xh = (xd - mean) * rstd
+    gm, bt = gamma.double(), beta.double()
+    r = dict(y=xh * gm + bt, stats=torch.cat([mean, rstd], 1), eps=eps, absx=xd.abs().mean(1), ex2=(xd * xd).mean(1),
+             var=var.reshape(-1), dx=None, dgamma=None, dbeta=None)
+    if dy is not None:
+        dyd = dy.double()
+        gd = dyd * gm
+        a = gd.mean(1, keepdim=True)
+        b = (gd * xh).mean(1, keepdim=True)
+        dx = rstd * (gd - a - xh * b)
+        r.update(dx=dx + dadd.double() if dadd is not None else dx, dgamma=(dyd * xh).sum(0), dbeta=dyd.sum(0),
+                 mag_g=(dyd * xh).abs().sum(0), mag_b=dyd.abs().sum(0))
+    return r
+
+
+def ln_dparam_reference(x, dy, stats):
+    """pso_layer_norm_dparam's own reference: its inputs are x, dy AND the fp32 statistics, so the fp64 sums are taken
+    with the statistics it is handed (with fp64 ones, their fp32 rounding -- an input rounding, 2^-24 |mean| against
+    an |x - mean| that may be far smaller -- would be charged to the kernel; at M = 1 nothing averages it out).
+    Returns dgamma, dbeta and the bound's magnitudes mag_g, mag_b."""
+    t = dy.double() * (x.double() - stats[:, :1].double()) * stats[:, 1:].double()
+    return dict(dgamma=t.sum(0), dbeta=dy.double().sum(0), mag_g=t.abs().sum(0), mag_b=dy.double().abs().sum(0))
+
+
+def layer_norm_fp64(x, gamma, beta, eps, dy, dadd):
+    """(y, stats[M, 2], dx, dgamma, dbeta) in fp64."""
+    r = ln_reference(x, gamma, beta, eps, dy, dadd)
+    return r["y"], r["stats"], r["dx"], r["dgamma"], r["dbeta"]
+
+
+# ---- the rounding models: norm.hip's documented roundings in plain torch fp32 ----------------------------------------
+def gn_chunk_sums(v, rows):
+    """fp32 per-channel sums of v [B, HW, C] (fp32) over blocks of `rows` pixel rows -> [B, blocks, C]: what one
+    workgroup of gn_partial_kernel leaves in its workspace row (torch's summation order, not the kernel's; the ragged
+    last block is padded with zeros, which add exactly)."""
+    B, HW, C = v.shape
+    nch = -(-HW // rows)
+    v = torch.nn.functional.pad(v, (0, 0, 0, nch * rows - HW))
+    return v.reshape(B, nch, rows, C).sum(2)
+
+
+def gn_group_combine(ch, G):
+    """per-channel block sums [B, blocks, C] fp32 -> fp32 sum over the Cg channels of a group, then gn_finalize_kernel's
+    fp64 combine over the blocks -> [B, G] fp64."""
+    B, nch, C = ch.shape
+    return ch.reshape(B, nch, G, C // G).sum(3).double().sum(1)
+
+
+def gn_stats_from_sums(a, q, n, eps):
+    """gn_finalize_kernel<false>: mean = a / n, var = q / n - mean^2 clamped at 0, both in fp64; (mean, rstd) rounded to
+    fp32 -> [B, G, 2]."""
+    mean = a / n
+    var = (q / n - mean * mean).clamp_min(0.0)
+    return torch.stack([mean, 1.0 / torch.sqrt(var + eps)], -1).float()
+
+
+def _per_channel(t, Cg):
+    return t.repeat_interleave(Cg, 1).unsqueeze(1)   # [B, G] -> [B, 1, C]
+
+
+def _gn_dz(xf, dy, stats, gm, bt, Cg, silu):
+    """xhat and dz = dy silu'(z) as gn_apply_bwd_kernel forms them from fp32 (mean, rstd): xhat = x rstd - mean rstd,
+    z = x (rstd gamma) + (beta - mean rstd gamma)."""
+    mean, rstd = _per_channel(stats[..., 0], Cg), _per_channel(stats[..., 1], Cg)
+    xh = xf * rstd + (-mean * rstd)
+    dz = dy.float()
+    if silu:
+        z = xf * (rstd * gm) + (bt - mean * rstd * gm)
+        dz = dz * _silu_parts(z)[1]
+    return xh, dz
+
+
+def gn_model_coef(x, dy, stats, gamma, beta, G, silu):
+    """The backward's fp32 group coefficients (mean(dz gamma), mean(dz gamma xhat)) [B, G, 2] from fp32 64-row block
+    sums, and the per-channel block sums [B, blocks, C] of dz and dz xhat that dbeta / dgamma are added up from."""
+    B, HW, C = x.shape
+    Cg = C // G
+    gm = gamma.float() if gamma is not None else torch.ones(C, device=x.device)
+    bt = beta.float() if beta is not None else torch.zeros(C, device=x.device)
+    xh, dz = _gn_dz(x.float(), dy, stats, gm, bt, Cg, silu)
+    c1, c2 = gn_chunk_sums(dz, GN_ROWS), gn_chunk_sums(dz * xh, GN_ROWS)
+    n = float(HW * Cg)
+    coef = torch.stack([gn_group_combine(c1 * gm, G) / n, gn_group_combine(c2 * gm, G) / n], -1).float()
+    return coef, c1, c2
+
+
+def group_norm_model(x, gamma, beta, G, eps, silu, dy=None, dadd=None, stats=None, coef=None):
+    """norm.hip's GroupNorm in plain torch: fp32 sums of x and x^2 per block of pixel rows and group, an fp64 combine
+    over the blocks, var = E[x^2] - mean^2 clamped at 0, statistics rounded to fp32, y = silu?(x (rstd gamma) +
+    (beta - mean rstd gamma)) rounded to the element type; dx = P dz + Q + R xhat (+ dadd) with P = rstd gamma,
+    Q = -rstd mean(dz gamma), R = -rstd mean(dz gamma xhat) from fp32 block sums, rounded to the element type; dgamma /
+    dbeta the fp64 sum of the fp32 per-channel block sums, rounded to fp32.  Returns (y, stats, dx, dgamma, dbeta).
+    stats / coef: use these instead of the model's own (the self-test's wrong restatements)."""
+    B, HW, C = x.shape
+    Cg = C // G
+    et = x.dtype
+    xf = x.float()
+    if stats is None:
+        rows = gn_rows_fwd(HW)
+        stats = gn_stats_from_sums(gn_group_combine(gn_chunk_sums(xf, rows), G),
+                                   gn_group_combine(gn_chunk_sums(xf * xf, rows), G), float(HW * Cg), eps)
+    gm = gamma.float() if gamma is not None else torch.ones(C, device=x.device)
+    bt = beta.float() if beta is not None else torch.zeros(C, device=x.device)
+    mean, rstd = _per_channel(stats[..., 0], Cg), _per_channel(stats[..., 1], Cg)
+    z = xf * (rstd * gm) + (bt - mean * rstd * gm)
+    y = (_silu_parts(z)[0] if silu else z).to(et)
+    if dy is None:
+        return y, stats, None, None, None
+    own, c1, c2 = gn_model_coef(x, dy, stats, gamma, beta, G, silu)
+    coef = own if coef is None else coef
+    xh, dz = _gn_dz(xf, dy, stats, gm, bt, Cg, silu)
+    ca, cb = _per_channel(coef[..., 0], Cg), _per_channel(coef[..., 1], Cg)
+    dx = (rstd * gm) * dz + ((-rstd * cb) * xh + (-rstd * ca))
+    if dadd is not None:
+        dx = dx + dadd.float()
+    return y, stats, dx.to(et), c2.double().sum((0, 1)).float(), c1.double().sum((0, 1)).float()
+
+
+def layer_norm_model(x, gamma, beta, eps, dy=None, dadd=None):
+    """norm.hip's LayerNorm in plain torch fp32: mean, then a centred variance and rsqrt; y = (x - mean) rstd gamma +
+    beta; dx = rstd (g - a - xhat b) + dadd with g = dy gamma, a = mean(g), b = mean(g xhat); outputs rounded to the
+    element type.  dgamma / dbeta as ln_dparam_part_kernel forms the terms: dy (x - mean) rstd and dy, summed in fp32.
+    Returns (y, stats[M, 2], dx, dgamma, dbeta)."""
+    M, C = x.shape
+    et = x.dtype
+    xf, gf, bf = x.float(), gamma.float(), beta.float()
+    mean = xf.sum(1, keepdim=True) / C
+    d = xf - mean
+    rstd = torch.rsqrt((d * d).sum(1, keepdim=True) / C + eps)
+    y = (d * rstd * gf + bf).to(et)
+    stats = torch.cat([mean, rstd], 1)
+    if dy is None:
+        return y, stats, None, None, None
+    xh = d * rstd
+    gd = dy.float() * gf
+    a = gd.sum(1, keepdim=True) / C
+    b = (gd * xh).sum(1, keepdim=True) / C
+    dx = rstd * (gd - a - xh * b)
+    if dadd is not None:
+        dx = dx + dadd.float()
+    return y, stats, dx.to(et), (dy.float() * d * rstd).sum(0), dy.float().sum(0)
+
+
+# ---- the same sums in the kernels' own order (the self-test derives F and F2 from these) ------------------------------
+def _seq_sum(v, dim):
+    """Left-to-right fp32 sum along `dim`, one rounded add per element, starting from 0 as the kernels' accumulators do."""
+    acc = torch.zeros_like(v.select(dim, 0))
+    for i in range(v.shape[dim]):
+        acc = acc + v.select(dim, i)
+    return acc
+
+
+def gn_chunk_sums_kernel_order(v, rows):
+    """gn_chunk_sums with gn_partial_kernel's chains: row slot s of RS adds the block's rows s, s + RS, ... in order,
+    then the RS slots are added in order."""
+    B, HW, C = v.shape
+    rs = gn_slots(C)
+    nch, per = -(-HW // rows), -(-rows // rs)
+    v = torch.nn.functional.pad(v, (0, 0, 0, nch * rows - HW)).reshape(B, nch, rows, C)
+    v = torch.nn.functional.pad(v, (0, 0, 0, per * rs - rows)).reshape(B, nch, per, rs, C)
+    return _seq_sum(_seq_sum(v, 2), 2)
+
+
+def gn_group_combine_kernel_order(ch, G):
+    B, nch, C = ch.shape
+    return _seq_sum(ch.reshape(B, nch, G, C // G), 3).double().sum(1)
+
+
+def gn_kernel_order(x, gamma, beta, G, eps, silu, dy):
+    """(stats, dgamma, dbeta) with every fp32 sum in the kernels' order: the forward's statistics, and the backward's
+    per-channel sums from those statistics (the single-pass and the split dparam reductions both add the block sums in
+    fp64, where the order no longer shows)."""
+    B, HW, C = x.shape
+    Cg = C // G
+    xf = x.float()
+    rows = gn_rows_fwd(HW)
+    stats = gn_stats_from_sums(gn_group_combine_kernel_order(gn_chunk_sums_kernel_order(xf, rows), G),
+                               gn_group_combine_kernel_order(gn_chunk_sums_kernel_order(xf * xf, rows), G),
+                               float(HW * Cg), eps)
+    gm = gamma.float() if gamma is not None else torch.ones(C)
+    bt = beta.float() if beta is not None else torch.zeros(C)
+    xh, dz = _gn_dz(xf, dy, stats, gm, bt, Cg, silu)
+    c1, c2 = gn_chunk_sums_kernel_order(dz, GN_ROWS), gn_chunk_sums_kernel_order(dz * xh, GN_ROWS)
+    return stats, c2.double().sum((0, 1)).float(), c1.double().sum((0, 1)).float()
+
+
+def _lane_sum(v):
+    """One wave's sum as ln_*_kernel takes it: v [M, C] fp32, lane l holds the 8-channel chunks l, l + 64, ... and adds
+    their elements in order; then the xor butterfly over the 64 lanes (32, 16, ... 1: a balanced tree)."""
+    M, C = v.shape
+    c8 = C // 8
+    maxv = -(-c8 // 64)
+    v = torch.nn.functional.pad(v.reshape(M, c8, 8), (0, 0, 0, maxv * 64 - c8)).reshape(M, maxv, 64, 8)
+    s = _seq_sum(v.permute(0, 2, 1, 3).reshape(M, 64, maxv * 8), 2)
+    w = 32
+    while w:
+        s = s[:, :w] + s[:, w:2 * w]
+        w //= 2
+    return s   # [M, 1]
+
+
+def ln_stats_kernel_order(x, eps):
+    xf = x.float()
+    C = x.shape[1]
+    mean = _lane_sum(xf) / C
+    d = xf - mean
+    return torch.cat([mean, torch.rsqrt(_lane_sum(d * d) / C + eps)], 1)
+
+
+def ln_dparam_plan(M):
+    """ordered_reduce_plan of fullgrad.hip for the M / 64 row blocks: (row blocks, splits, blocks per split)."""
+    nb = -(-M // LN_DPARAM_ROWS)
+    if nb <= 48:
+        return nb, nb, 1
+    S = min(64, max(1, (nb + 31) // 32))
+    ch = -(-nb // S)
+    return nb, -(-nb // ch), ch
+
+
+def ln_dparam_kernel_order(x, dy, stats, prev_g, prev_b):
+    """pso_layer_norm_dparam_ws in its own order: a thread adds rows r0 + ty, r0 + ty + 4, ... of its 64-row block, the
+    4 slices are added in order, the blocks of a split in order, the splits in order, then out += acc."""
+    M, C = x.shape
+    nb, S, ch = ln_dparam_plan(M)
+    d = dy.float()
+    t = torch.stack([d * (x.float() - stats[:, :1]) * stats[:, 1:], d], 0)               # [2, M, C]
+    t = torch.nn.functional.pad(t, (0, 0, 0, nb * LN_DPARAM_ROWS - M)).reshape(2, nb, LN_DPARAM_ROWS // 4, 4, C)
+    part = _seq_sum(t, 2)
+    part = ((part[:, :, 0] + part[:, :, 1]) + part[:, :, 2]) + part[:, :, 3]              # [2, nb, C]
+    if ch > 1:
+        part = _seq_sum(torch.nn.functional.pad(part, (0, 0, 0, S * ch - nb)).reshape(2, S, ch, C), 2)
+    acc = _seq_sum(part, 1)
+    return prev_g + acc[0], prev_b + acc[1]
+
+
+# ---- bounds and checks ------------------------------------------------------------------------------------------------
+def norm_stats_units(stats, ref):
+    """Worst error of saved statistics [..., 2] against gn_reference / ln_reference, per group or row, in units of
+    2^-23 mean|x| (the mean) and of 2^-23 (E[x^2] + eps) / (var + eps) (rstd, relative): (mean_units, rstd_units).  The
+    bound is NORM_F units.  A NaN comes back as NaN, which fails `<=`."""
+    em = (stats[..., 0].double() - ref["stats"][..., 0]).abs() / (U32 * ref["absx"]).clamp_min(_TINY)
+    er = (stats[..., 1].double() / ref["stats"][..., 1] - 1).abs() / (U32 * (ref["ex2"] + ref["eps"])
+                                                                        / (ref["var"] + ref["eps"]))
+    return em.max().item(), er.max().item()
+
+
+def norm_dparam_bounds(ref, prevs, f2=None):
+    """(dgamma bound, dbeta bound) [C]: f2 2^-23 sum|dz xhat| and f2 2^-23 sum|dz| (f2: NORM_F2_CENTRED unless given),
+    plus 2^-23 |previous contents| (prevs: {"dgamma": ..., "dbeta": ...}, either may be missing) where the kernel adds
+    to them."""
+    out = []
+    f2 = NORM_F2_CENTRED if f2 is None else f2
+    for name, mag in (("dgamma", "mag_g"), ("dbeta", "mag_b")):
+        b = f2 * U32 * ref[mag]
+        out.append(b + U32 * prevs[name].double().abs() if name in prevs else b)
+    return tuple(out)
+
+
+def norm_dparam_units(got, ref, prevs):
+    """{name: worst error} of the parameter gradients in `got` ({"dgamma": ..., "dbeta": ...}, either may be missing)
+    in units of 2^-23 sum|dz xhat| / 2^-23 sum|dz|; previous contents are added to the reference first and their
+    rounding allowance 2^-23 |prev| is taken off the error.  The bound is NORM_F2_CENTRED (shifted: NORM_F2) units."""
+    out = {}
+    for name, mag in (("dgamma", "mag_g"), ("dbeta", "mag_b")):
+        if name not in got:
+            continue
+        prev = prevs[name].double() if name in prevs else torch.zeros_like(ref[name])
+        err = (got[name].double() - (ref[name] + prev)).abs() - U32 * prev.abs()
+        out[name] = (err / (U32 * ref[mag]).clamp_min(_TINY)).max().item()
+    return out
+
+
+def _vec_violations(got, ref, bound):
+    return violations(got.reshape(1, -1), ref.reshape(1, -1), bound.reshape(1, -1))
+
+
+def norm_chunk_bounds(model, ref):
+    """worst 8-chunk of the model's y and dx against fp64: ROW_BOUND_FACTOR x these are the kernels' bounds."""
+    return {"y": rowwise_rel(model[0], ref["y"], 8), "dx": rowwise_rel(model[2], ref["dx"], 8)}
+
+
+def _assert_norm_outputs(tag, got, stats, dparams, ref, model, prevs, f2=None):
+    """Assertions 2 - 5 of a norm case (1, the guard bands, is the caller's): finite, statistics, chunks, dparams."""
+    worst = norm_chunk_bounds(model, ref)
+    mu, ru = norm_stats_units(stats, ref)
+    mmu, mru = norm_stats_units(model[1], ref)
+    line = [f"{n} kernel {rowwise_rel(t, ref[n], 8)} model {worst[n]}" for n, t in got.items()]
+    line.append(f"stats units mean {mu:.2f} rstd {ru:.2f} (model {mmu:.2f} {mru:.2f}, bound {NORM_F:g})")
+    if dparams:
+        ug = norm_dparam_units(dparams, ref, prevs)
+        line.append("dparam units " + " ".join(f"{n} {u:.2f}" for n, u in ug.items())
+                    + f" (bound {NORM_F2_CENTRED if f2 is None else f2:g})")
+    print(f"\n[norm {tag}] " + "; ".join(line), flush=True)
+    for n, t in got.items():
+        assert torch.isfinite(t.float()).all(), (tag, n)                                          # 2.
+    assert torch.isfinite(stats).all(), (tag, "stats")
+    assert mu <= NORM_F and ru <= NORM_F, (f"{tag} stats: mean {mu:.2f}, rstd {ru:.2f} units of the derived bound, "
+                                           f"allowed {NORM_F:g}")                                    # 3.
+    for n, t in got.items():                                                                      # 4.
+        e, bound = rowwise_rel(t, ref[n], 8), ROW_BOUND_FACTOR * worst[n]
+        assert e < bound, f"{tag} {n}: worst 8-chunk {e}, bound {bound:.3e} = 3 x model {worst[n]}"
+    bg, bb = norm_dparam_bounds(ref, prevs, f2)
+    for n, bound in (("dgamma", bg), ("dbeta", bb)):                                              # 5.
+        if n in dparams:
+            assert torch.isfinite(dparams[n]).all(), (tag, n)
+            want = ref[n] + (prevs[n].double() if n in prevs else 0)
+            cnt, msg = _vec_violations(dparams[n], want, bound)
+            assert cnt == 0, f"{tag} {n}: {msg}"
+
+
+def _fill_guarded(rows, widths, src, device, gap=8):
+    """guarded() views holding copies of the [rows, w] tensors in src; returns (views, check)."""
+    views, check = guarded(rows, widths, gap=gap, dtype=src[0].dtype, device=device)
+    for v, s in zip(views, src):
+        v.copy_(s.reshape(rows, -1))
+    return views, check
+
+
+def run_group_norm_case(cuda, B, HW, C, G, silu, affine=True, shifted=False, accumulate=False,
+                        want=("dgamma", "dbeta")):
+    """One GroupNorm case of tests/test_gpu_norm_parity.py (and of the fp16 library's in tests/test_gpu_f16.py):
+    forward and backward with dadd, inputs that end where the payload NaNs begin, outputs in guarded buffers, fp32
+    parameter gradients in guarded buffers over non-zero previous contents, the five assertions."""
+    from pairwise_sample_optimization_amd import kernels as K
+    tag = f"gn {K.ELEM} {(B, HW, C, G)} silu={silu}" + (" no-affine" if not affine else "") \
+        + (" shifted" if shifted else "") + (" accumulate" if accumulate else "") + f" {'+'.join(want)}"
+    inp = norm_inputs("gn", (B, HW, C, G), K.ELEM, "cpu", shifted)
+    ins, checks = {}, []
+    for n in ("x", "dy", "dadd"):   # gap = 0: the row after the last one is fill, so a read past the end shows
+        (v,), chk = _fill_guarded(B * HW, [C], [inp[n]], cuda, gap=0)
+        ins[n] = v.view(B, HW, C)
+        checks.append((n, chk))
+    x, dy, dadd = ins["x"], ins["dy"], ins["dadd"]
+    gamma, beta = (inp["gamma"].to(cuda), inp["beta"].to(cuda)) if affine else (None, None)
+    ref = gn_reference(x, gamma, beta, G, NORM_EPS, silu, dy, dadd)
+    model = group_norm_model(x, gamma, beta, G, NORM_EPS, silu, dy, dadd)
+    (y2,), chk_y = guarded(B * HW, [C], gap=0, device=cuda)
+    (dx2,), chk_dx = guarded(B * HW, [C], gap=0, device=cuda)
+    checks += [("y", chk_y), ("dx", chk_dx)]
+    gen = torch.Generator().manual_seed(_seed(B, HW, C, G, 7))
+    prevs, outs = {}, {}
+    for n in want:   # non-zero previous contents either way: without accumulate they must not show
+        prev = torch.randn(C, generator=gen).to(cuda)
+        (v,), chk = _fill_guarded(1, [C], [prev], cuda)
+        outs[n] = v[0]
+        checks.append((n, chk))
+        if accumulate:
+            prevs[n] = prev
+    y, stats = K.group_norm_fwd(x, gamma, beta, G, NORM_EPS, silu, out=y2.view(B, HW, C))
+    dx = K.group_norm_bwd(x, dy, stats, gamma, beta, silu, dadd=dadd, dgamma=outs.get("dgamma"),
+                          dbeta=outs.get("dbeta"), accumulate=accumulate, out=dx2.view(B, HW, C))
+    torch.cuda.synchronize()
+    assert y.data_ptr() == y2.data_ptr() and dx.data_ptr() == dx2.data_ptr() and stats.shape == (B, G, 2)
+    for n, chk in checks:                                                                         # 1.
+        chk(f"{tag} {n}")
+    for n in ("x", "dy", "dadd"):
+        assert torch.equal(ins[n].cpu().view(torch.int16), inp[n].view(torch.int16)), f"{tag}: input {n} was written"
+    _assert_norm_outputs(tag, {"y": y, "dx": dx}, stats, outs, ref, model, prevs, NORM_F2 if shifted else None)
+
+
+def run_layer_norm_case(cuda, M, C):
+    """One LayerNorm case: x, dy, dadd column slices of guarded buffers (16-byte aligned, ld > C, three different ld),
+    y and dx written into guarded slices through out=, backward with dadd as unet.py calls it, the five assertions
+    (dgamma / dbeta have their own cases: run_ln_dparam_case)."""
+    from pairwise_sample_optimization_amd import kernels as K
+    tag = f"ln {K.ELEM} {(M, C)}"
+    inp = norm_inputs("ln", (M, C), K.ELEM, "cpu")
+    ins, checks = {}, []
+    for n, gap in (("x", 8), ("dy", 16), ("dadd", 24)):
+        (v,), chk = _fill_guarded(M, [C], [inp[n]], cuda, gap=gap)
+        ins[n] = v
+        checks.append((n, chk))
+    x, dy, dadd = ins["x"], ins["dy"], ins["dadd"]
+    assert len({t.stride(0) for t in (x, dy, dadd)}) == 3 and all(t.stride(0) > C for t in (x, dy, dadd))
+    gamma, beta = inp["gamma"].to(cuda), inp["beta"].to(cuda)
+    ref = ln_reference(x, gamma, beta, NORM_EPS, dy, dadd)
+    model = layer_norm_model(x, gamma, beta, NORM_EPS, dy, dadd)
+    (yv,), chk_y = guarded(M, [C], device=cuda)
+    (_, dxv), chk_dx = guarded(M, [C, C], device=cuda)   # the second slice: ld = 2 C + 24
+    checks += [("y", chk_y), ("dx", chk_dx)]
+    y, stats = K.layer_norm_fwd(x, gamma, beta, NORM_EPS, out=yv)
+    dx = K.layer_norm_bwd(x, dy, stats, gamma, dadd=dadd, out=dxv)
+    torch.cuda.synchronize()
+    assert y.data_ptr() == yv.data_ptr() and dx.data_ptr() == dxv.data_ptr() and stats.shape == (M, 2)
+    for n, chk in checks:                                                                         # 1.
+        chk(f"{tag} {n}")
+    for n in ("x", "dy", "dadd"):
+        assert torch.equal(ins[n].cpu().view(torch.int16), inp[n].view(torch.int16)), f"{tag}: input {n} was written"
+    _assert_norm_outputs(tag, {"y": y, "dx": dx}, stats, {}, ref, model, {})
+
+
+def run_ln_dparam_case(cuda, M, C, strided):
+    """One case of the ordered LayerNorm parameter gradients (K.layer_norm_dparam, the product path): statistics handed
+    over as the fp32 rounding of the fp64 ones (ln_dparam_reference is taken with them), dgamma / dbeta in guarded fp32 buffers over non-zero contents (the op
+    accumulates); zero violations of the derived bound, and the same bits on a second call."""
+    from pairwise_sample_optimization_amd import kernels as K
+    tag = f"ln dparam {K.ELEM} {(M, C)}" + (" strided" if strided else "")
+    inp = norm_inputs("ln", (M, C), K.ELEM, "cpu")
+    if strided:
+        (x,), _ = _fill_guarded(M, [C], [inp["x"]], cuda, gap=8)
+        (dy,), _ = _fill_guarded(M, [C], [inp["dy"]], cuda, gap=16)
+        assert x.stride(0) > C and dy.stride(0) > C and x.stride(0) != dy.stride(0)
+    else:
+        x, dy = inp["x"].to(cuda), inp["dy"].to(cuda)
+    stats = ln_reference(x, inp["gamma"].to(cuda), inp["beta"].to(cuda), NORM_EPS)["stats"].float()
+    ref = ln_dparam_reference(x, dy, stats)
+    gen = torch.Generator().manual_seed(_seed(M, C, 11))
+    prevs = {n: torch.randn(C, generator=gen).to(cuda) for n in ("dgamma", "dbeta")}
+    runs = []
+    for _ in range(2):
+        outs, checks = {}, []
+        for n in ("dgamma", "dbeta"):
+            (v,), chk = _fill_guarded(1, [C], [prevs[n]], cuda)
+            outs[n] = v[0]
+            checks.append((n, chk))
+        K.layer_norm_dparam(x, dy, stats, outs["dgamma"], outs["dbeta"])
+        torch.cuda.synchronize()
+        for n, chk in checks:
+            chk(f"{tag} {n}")
+        runs.append(outs)
+    outs = runs[0]
+    ug = norm_dparam_units(outs, ref, prevs)
+    print(f"\n[norm {tag}] plan (blocks, splits, per split) {ln_dparam_plan(M)}; units dgamma {ug['dgamma']:.2f} dbeta "
+          f"{ug['dbeta']:.2f} (bound {NORM_F2_CENTRED:g})", flush=True)
+    bg, bb = norm_dparam_bounds(ref, prevs)
+    for n, bound in (("dgamma", bg), ("dbeta", bb)):
+        assert torch.isfinite(outs[n]).all(), (tag, n)
+        cnt, msg = _vec_violations(outs[n], ref[n] + prevs[n].double(), bound)
+        assert cnt == 0, f"{tag} {n}: {msg}"
+        assert torch.equal(runs[0][n], runs[1][n]), f"{tag} {n}: a second call gave other bits"

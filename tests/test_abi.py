@@ -101,6 +101,56 @@ def test_attention_bwd_checks_output_alignment_and_split_batch_stride():
             assert msg.startswith("pso_attention_bwd: ") and want in msg, (pso_lib, name, msg)
 
 
+_LN_ARG_PROBE = """
+import torch
+from pairwise_sample_optimization_amd import _lib
+assert not torch.cuda.is_available()
+l = _lib.lib()
+M, C = 5, 640
+P = [0x10000 * (i + 1) for i in range(5)]   # fake, never dereferenced: every case fails a check before any launch
+fwd = dict(x=P[0], ldx=C, gamma=P[1], beta=P[2], y=P[3], ldy=C)
+for name, bad in [("x+8B", dict(x=P[0] + 8)), ("y+2B", dict(y=P[3] + 2)), ("gamma+8B", dict(gamma=P[1] + 8)),
+                  ("beta+4B", dict(beta=P[2] + 4)), ("ldx%8", dict(ldx=C + 4)), ("ldy%8", dict(ldy=C + 12))]:
+    a = dict(fwd, **bad)
+    rc = l.pso_layer_norm_fwd(M, C, 1e-5, a["x"], a["ldx"], a["gamma"], a["beta"], a["y"], a["ldy"], P[4], None)
+    print("case fwd:" + name, rc, l.pso_last_error().decode())
+bwd = dict(x=P[0], ldx=C, dy=P[1], lddy=C, gamma=P[2], dadd=P[3], ldadd=C, dx=P[4], lddx=C)
+for name, bad in [("x+8B", dict(x=P[0] + 8)), ("dy+8B", dict(dy=P[1] + 8)), ("gamma+2B", dict(gamma=P[2] + 2)),
+                  ("dadd+8B", dict(dadd=P[3] + 8)), ("dx+4B", dict(dx=P[4] + 4)), ("ldx%8", dict(ldx=C + 4)),
+                  ("lddy%8", dict(lddy=C + 4)), ("ldadd%8", dict(ldadd=C + 4)), ("lddx%8", dict(lddx=C + 2))]:
+    a = dict(bwd, **bad)
+    rc = l.pso_layer_norm_bwd(M, C, a["x"], a["ldx"], a["dy"], a["lddy"], 0x90000, a["gamma"], a["dadd"], a["ldadd"],
+                              a["dx"], a["lddx"], None)
+    print("case bwd:" + name, rc, l.pso_last_error().decode())
+"""
+
+
+def test_layer_norm_checks_row_alignment_of_every_operand():
+    """pso_layer_norm_fwd / _bwd read and write every row as 16-byte chunks: a base pointer off a 16-byte boundary or
+    an ld that is no multiple of 8 elements is refused with PSO_ERR_ARG and a message that names the rule, for each
+    operand in turn (gamma, beta and dadd included), in all three library builds.  Host-only, like the attention
+    probe above: with a GPU present a regression would launch on the fake pointers."""
+    import sys
+    import pytest
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("argument checks are exercised where no launch can follow a regression (no GPU)")
+    for pso_lib in (None, "knobs", "f16"):
+        env = {k: v for k, v in os.environ.items() if k not in ("PSO_LIB", "PSO_LIB_PATH")}
+        if pso_lib:
+            env["PSO_LIB"] = pso_lib
+        r = subprocess.run([sys.executable, "-c", _LN_ARG_PROBE], env=env, cwd=ROOT, capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode == 0, (pso_lib, r.stdout[-2000:] + r.stderr[-2000:])
+        got = {m.group(1): (int(m.group(2)), m.group(3))
+               for m in re.finditer(r"^case (\S+) (-?\d+) (.*)$", r.stdout, flags=re.M)}
+        assert len(got) == 15, (pso_lib, r.stdout)
+        for name, (rc, msg) in got.items():
+            assert rc == 1, (pso_lib, name, rc, msg)  # PSO_ERR_ARG
+            entry = "pso_layer_norm_fwd: " if name.startswith("fwd:") else "pso_layer_norm_bwd: "
+            assert msg.startswith(entry) and "16-B aligned rows" in msg, (pso_lib, name, msg)
+
+
 def test_product_library_has_no_benchmark_knobs():
     """the benchmark knobs (include/pso_amd_knobs.h) and the measured-not-kept kernel forms live in the
     tools build only.  The product library exports none of the knob setters, reads no environment variable, and holds

@@ -325,6 +325,22 @@ def test_layer_norm_fwd_bwd(cuda):
     _yardstick("layer norm dx", dx, g16, g32)
 
 
+@pytest.mark.parametrize("silu", [False, True])
+@pytest.mark.parametrize("B,HW,C,G", [(2, 100, 320, 32), (1, 130, 1920, 32)])
+def test_group_norm_localised(cuda, B, HW, C, G, silu):
+    """Two GroupNorm cases of tests/test_gpu_norm_parity.py on the fp16 library (Cg = 10 across the 8-chunks; the
+    480-thread block): saved statistics, per-chunk y / dx within 3 x the fp16 rounding model, dgamma / dbeta, guards."""
+    import parity_util as P
+    P.run_group_norm_case(cuda, B, HW, C, G, silu)
+
+
+def test_layer_norm_localised(cuda):
+    """The (7, 520) LayerNorm case of tests/test_gpu_norm_parity.py on the fp16 library: one chunk into MAXV = 2,
+    strided inputs, guarded outputs."""
+    import parity_util as P
+    P.run_layer_norm_case(cuda, 7, 520)
+
+
 def test_geglu_elementwise_fwd_bwd(cuda):
     from pairwise_sample_optimization_amd import kernels as Kk
     g = _gen(14)

@@ -2,6 +2,9 @@
 checked here, with no kernel involved -- the rounding model against fp64 on every attention shape the GPU tests use,
 the guard-band detector, the reason the per-row metric exists, and the derived GEGLU / GEMM element-wise bounds against
 a torch restatement of the documented computation (zero violations)."""
+import functools
+import math
+
 import pytest
 import torch
 
@@ -127,3 +130,207 @@ def test_gemm_bound_holds_for_the_restatement(case):
     n, msg = P.violations(got, ref, bound)
     assert n == 0, msg
     assert P.violations(torch.roll(got, 1, 1), ref, bound)[0] > got.numel() // 2
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# GroupNorm / LayerNorm helpers
+# ----------------------------------------------------------------------------------------------------------------------
+_DTYPES = pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
+
+
+def _gn_named():
+    """Every GroupNorm configuration tests/test_gpu_norm_parity.py runs: (shape, silu, affine, shifted)."""
+    for shape in P.GN_CASES:
+        for silu in (False, True):
+            yield shape, silu, True, False
+    for silu in (False, True):
+        yield P.GN_NOAFFINE_CASE, silu, False, False
+        yield P.GN_SHIFTED_CASE, silu, True, True
+    for B, HW in P.GN_DPARAM_CASES:
+        yield (B, HW, 64, 32), True, True, False
+
+
+def _gn_case(shape, silu, affine, shifted, dtype):
+    inp = P.norm_inputs("gn", shape, dtype, "cpu", shifted)
+    gamma, beta = (inp["gamma"], inp["beta"]) if affine else (None, None)
+    return inp, gamma, beta, P.gn_reference(inp["x"], gamma, beta, shape[3], P.NORM_EPS, silu, inp["dy"], inp["dadd"])
+
+
+@functools.lru_cache(maxsize=None)
+def _ln_case(M, C, dtype):
+    inp = P.norm_inputs("ln", (M, C), dtype, "cpu")
+    return inp, P.ln_reference(inp["x"], inp["gamma"], inp["beta"], P.NORM_EPS, inp["dy"], inp["dadd"])
+
+
+def _check_model(tag, model, ref, dtype, f2=None):
+    """The four points every named case must meet: finite, worst chunk of rounding size, statistics inside the derived
+    bound, no parameter gradient outside its own."""
+    y, stats, dx, dgamma, dbeta = model
+    assert all(torch.isfinite(t.float()).all() for t in model), tag
+    assert all(torch.isfinite(ref[n]).all() for n in ("y", "stats", "dx", "dgamma", "dbeta")), tag
+    worst = P.norm_chunk_bounds(model, ref)
+    mu, ru = P.norm_stats_units(stats, ref)
+    ug = P.norm_dparam_units({"dgamma": dgamma, "dbeta": dbeta}, ref, {})
+    print(f"{tag}: y {worst['y']}, dx {worst['dx']}, stats units {mu:.2f} {ru:.2f}, dparam units {ug}")
+    for n, e in worst.items():
+        assert 0 < e < 4 * P.ELEM_ULP[dtype], (tag, n, e)
+    assert mu <= P.NORM_F and ru <= P.NORM_F, (tag, mu, ru)
+    bg, bb = P.norm_dparam_bounds(ref, {}, f2)
+    assert P.violations(dgamma.reshape(1, -1), ref["dgamma"].reshape(1, -1), bg.reshape(1, -1))[0] == 0, tag
+    assert P.violations(dbeta.reshape(1, -1), ref["dbeta"].reshape(1, -1), bb.reshape(1, -1))[0] == 0, tag
+
+
+@_DTYPES
+def test_group_norm_model_against_fp64_on_every_named_case(dtype):
+    for shape, silu, affine, shifted in _gn_named():
+        inp, gamma, beta, ref = _gn_case(shape, silu, affine, shifted, dtype)
+        model = P.group_norm_model(inp["x"], gamma, beta, shape[3], P.NORM_EPS, silu, inp["dy"], inp["dadd"])
+        _check_model(f"gn {shape} silu={silu} affine={affine} shifted={shifted} {dtype}", model, ref, dtype,
+                     P.NORM_F2 if shifted else None)
+        for got, want in zip(P.group_norm_fp64(inp["x"], gamma, beta, shape[3], P.NORM_EPS, silu, inp["dy"],
+                                               inp["dadd"]), ("y", "stats", "dx", "dgamma", "dbeta")):
+            assert got.dtype == torch.float64 and torch.equal(got, ref[want])
+
+
+@_DTYPES
+def test_layer_norm_model_against_fp64_on_every_named_case(dtype):
+    for M, C in P.LN_CASES + [(m, c) for m, c, _ in P.LN_DPARAM_CASES]:
+        inp, ref = _ln_case(M, C, dtype)
+        if C % 8:   # the dparam-only shapes with a scalar tail: no 8-chunks to compare, the sums only
+            st, _, dg, db = P.layer_norm_model(inp["x"], inp["gamma"], inp["beta"], P.NORM_EPS, inp["dy"],
+                                               inp["dadd"])[1:]
+            ref = P.ln_dparam_reference(inp["x"], inp["dy"], st)
+            bg, bb = P.norm_dparam_bounds(ref, {})
+            assert P.violations(dg.reshape(1, -1), ref["dgamma"].reshape(1, -1), bg.reshape(1, -1))[0] == 0
+            assert P.violations(db.reshape(1, -1), ref["dbeta"].reshape(1, -1), bb.reshape(1, -1))[0] == 0
+            continue
+        model = P.layer_norm_model(inp["x"], inp["gamma"], inp["beta"], P.NORM_EPS, inp["dy"], inp["dadd"])
+        # the parameter gradients are an op of their own, whose inputs include the statistics: the model's here
+        ref = dict(ref, **P.ln_dparam_reference(inp["x"], inp["dy"], model[1]))
+        _check_model(f"ln {(M, C)} {dtype}", model, ref, dtype)
+
+
+def _f_from(worst):
+    """Four times the worst measured ratio, rounded up to a power of two, no smaller than 8."""
+    return max(8.0, 2.0 ** math.ceil(math.log2(4.0 * worst)))
+
+
+def test_norm_F_and_F2_come_from_the_kernel_order_restatement():
+    """NORM_F and NORM_F2 are derived here, not from a kernel run: every fp32 sum of every named case is restated with
+    the kernels' own sequential chain lengths (parity_util.*_kernel_order), in bf16 and fp16; the worst error in units
+    of the bound expressions is printed, and each constant must be 4 x its worst, rounded up to a power of two and no
+    smaller than 8."""
+    w_mean = w_rstd = w_dp = w_dpc = 0.0
+    gen = torch.Generator().manual_seed(5)
+    for dtype in (torch.bfloat16, torch.float16):
+        for shape, silu, affine, shifted in _gn_named():
+            inp, gamma, beta, ref = _gn_case(shape, silu, affine, shifted, dtype)
+            stats, dg, db = P.gn_kernel_order(inp["x"], gamma, beta, shape[3], P.NORM_EPS, silu, inp["dy"])
+            mu, ru = P.norm_stats_units(stats, ref)
+            ug = P.norm_dparam_units({"dgamma": dg, "dbeta": db}, ref, {})
+            w_mean, w_rstd = max(w_mean, mu), max(w_rstd, ru)
+            # accumulate=True: one more fp32 add onto the previous contents, with its own allowance
+            prev = {n: torch.randn(shape[2], generator=gen) for n in ("dgamma", "dbeta")}
+            ua = P.norm_dparam_units({"dgamma": prev["dgamma"] + dg, "dbeta": prev["dbeta"] + db}, ref, prev)
+            w_dp = max(w_dp, *ug.values(), *ua.values())
+            if not shifted:
+                w_dpc = max(w_dpc, *ug.values(), *ua.values())
+        for M, C in P.LN_CASES:
+            inp, ref = _ln_case(M, C, dtype)
+            mu, ru = P.norm_stats_units(P.ln_stats_kernel_order(inp["x"], P.NORM_EPS), ref)
+            w_mean, w_rstd = max(w_mean, mu), max(w_rstd, ru)
+        for M, C, _ in P.LN_DPARAM_CASES:
+            inp, ref = _ln_case(M, C, dtype)
+            prev = {n: torch.randn(C, generator=gen) for n in ("dgamma", "dbeta")}
+            stats = ref["stats"].float()
+            dg, db = P.ln_dparam_kernel_order(inp["x"], inp["dy"], stats, prev["dgamma"], prev["dbeta"])
+            ug = P.norm_dparam_units({"dgamma": dg, "dbeta": db}, P.ln_dparam_reference(inp["x"], inp["dy"], stats), prev)
+            w_dp, w_dpc = max(w_dp, *ug.values()), max(w_dpc, *ug.values())
+    print(f"\nkernel-order restatement, worst over every named case: mean {w_mean:.3f} units, rstd {w_rstd:.3f} units "
+          f"-> F = {_f_from(max(w_mean, w_rstd)):g}; dgamma / dbeta {w_dp:.3f} units -> F2 = {_f_from(w_dp):g}; "
+          f"without the shifted case {w_dpc:.3f} units -> F2 (centred) = {_f_from(w_dpc):g}")
+    assert 0 < w_mean and 0 < w_rstd and 0 < w_dpc <= w_dp
+    assert P.NORM_F == _f_from(max(w_mean, w_rstd)), (P.NORM_F, w_mean, w_rstd)
+    assert P.NORM_F2 == _f_from(w_dp), (P.NORM_F2, w_dp)
+    assert P.NORM_F2_CENTRED == _f_from(w_dpc), (P.NORM_F2_CENTRED, w_dpc)
+
+
+def test_ln_dparam_plan_reaches_the_named_regimes():
+    assert P.ln_dparam_plan(1) == (1, 1, 1) and P.ln_dparam_plan(65) == (2, 2, 1)
+    assert P.ln_dparam_plan(48 * 64) == (48, 48, 1)
+    assert P.ln_dparam_plan(3100) == (49, 2, 25)     # two levels, splits of 25 and 24 row blocks
+    assert P.ln_dparam_plan(4200) == (66, 3, 22)
+    assert [P.gn_slots(c) for c in (8, 32, 64, 128, 264, 320, 960, 1920, 4096)] == [512, 128, 64, 32, 8, 8, 4, 2, 1]
+    assert [(c // 8) * P.gn_slots(c) for c in (264, 960, 1920)] == [264, 480, 480]
+    assert P.gn_rows_fwd(16384) == 64 and P.gn_rows_fwd(16385) == 512
+    assert P.gn_edge_rows(100) == [0, 63, 64, 99] and P.gn_edge_rows(64) == [0, 63]
+    assert P.gn_edge_rows(16500) == [0, 63, 64, 511, 512, 16499]
+
+
+@_DTYPES
+def test_norm_detectors_wrong_statistics_land_outside_the_bound(dtype):
+    """Deliberately wrong restatements of the statistics, each far outside the bound a correct one meets: the last
+    pixel row left out, row 64 counted twice, the LayerNorm mean over C - 8 channels -- and, for contrast, the
+    whole-tensor ratio of the y they give, which the older 8e-3 bar lets through."""
+    B, HW, C, G = shape = (2, 100, 320, 32)
+    inp, gamma, beta, ref = _gn_case(shape, False, True, False, dtype)
+    x = inp["x"]
+    n = float(HW * (C // G))
+    good = P.group_norm_model(x, gamma, beta, G, P.NORM_EPS, False)
+    assert max(P.norm_stats_units(good[1], ref)) <= P.NORM_F
+    xf = x.float()
+
+    def sums(v):
+        return P.gn_group_combine(P.gn_chunk_sums(v, 64), G)
+
+    # (a) every block stops one row early: the image's last row never enters the sums (the divisor stays HW * Cg)
+    a, q = sums(xf[:, :HW - 1]), sums(xf[:, :HW - 1] ** 2)
+    lost = P.gn_stats_from_sums(a, q, n, P.NORM_EPS)
+    # (b) the row at the block boundary is taken by both blocks
+    a, q = sums(xf) + sums(xf[:, 64:65]), sums(xf * xf) + sums(xf[:, 64:65] ** 2)
+    twice = P.gn_stats_from_sums(a, q, n, P.NORM_EPS)
+    for name, bad in (("last row lost", lost), ("row 64 twice", twice)):
+        mu, ru = P.norm_stats_units(bad, ref)
+        print(f"{name} {dtype}: stats units mean {mu:.0f} rstd {ru:.0f} (bound {P.NORM_F:g})")
+        assert ru > 1000 * P.NORM_F / 8, (name, mu, ru)
+    # an unweighted row shows what the Frobenius bar cannot see: rstd off by percents of a percent, y inside 8e-3
+    plain = torch.randn(1, 100, 64).to(dtype)
+    pref = P.gn_reference(plain, None, None, 2, P.NORM_EPS, False)
+    pf = plain.float()
+    a = P.gn_group_combine(P.gn_chunk_sums(pf[:, :99], 64), 2)
+    q = P.gn_group_combine(P.gn_chunk_sums(pf[:, :99] ** 2, 64), 2)
+    bad = P.gn_stats_from_sums(a, q, 100.0 * 32, P.NORM_EPS)
+    ybad = P.group_norm_model(plain, None, None, 2, P.NORM_EPS, False, stats=bad)[0]
+    assert P.frob_rel(ybad, pref["y"]) < 8e-3 and P.norm_stats_units(bad, pref)[1] > 100 * P.NORM_F
+    # (c) LayerNorm statistics over C - 8 channels (a lane's last chunk masked off)
+    M, C = 7, 520
+    inp, ref = _ln_case(M, C, dtype)
+    good = P.layer_norm_model(inp["x"], inp["gamma"], inp["beta"], P.NORM_EPS)
+    assert max(P.norm_stats_units(good[1], ref)) <= P.NORM_F
+    xs = inp["x"].float()[:, :C - 8]
+    mean = xs.sum(1, keepdim=True) / C
+    bad = torch.cat([mean, torch.rsqrt(((xs - mean) ** 2).sum(1, keepdim=True) / C + P.NORM_EPS)], 1)
+    mu, ru = P.norm_stats_units(bad, ref)
+    print(f"LN mean over C - 8 {dtype}: stats units mean {mu:.0f} rstd {ru:.0f}")
+    assert mu > 1000 * P.NORM_F / 8 and ru > 1000 * P.NORM_F / 8
+
+
+@_DTYPES
+def test_norm_detector_neighbours_coefficients_land_outside_the_chunk_bound(dtype):
+    """dx with every group's backward coefficients taken from its neighbour (g -> g + 1): the whole-tensor ratio may
+    stay small, the worst 8-chunk leaves 3 x the model's by more than an order of magnitude."""
+    B, HW, C, G = shape = (2, 100, 320, 32)
+    inp, gamma, beta, ref = _gn_case(shape, True, True, False, dtype)
+    args = (inp["x"], gamma, beta, G, P.NORM_EPS, True, inp["dy"], inp["dadd"])
+    model = P.group_norm_model(*args)
+    bound = P.ROW_BOUND_FACTOR * P.norm_chunk_bounds(model, ref)["dx"]
+    coef, _, _ = P.gn_model_coef(inp["x"], inp["dy"], model[1], gamma, beta, G, True)
+    bad = P.group_norm_model(*args, coef=torch.roll(coef, 1, 1))
+    e = P.rowwise_rel(bad[2], ref["dx"], 8)
+    print(f"neighbour's coefficients {dtype}: worst dx chunk {e}, bound {bound:.3e}")
+    assert P.rowwise_rel(model[2], ref["dx"], 8) < bound < e and e > 0.1
+    # and one group only (group 5 of image 1 uses group 6's): found, and named
+    one = coef.clone()
+    one[1, 5] = coef[1, 6]
+    e = P.rowwise_rel(P.group_norm_model(*args, coef=one)[2], ref["dx"], 8)
+    assert e > bound and e.index[0] == 1 and e.index[2] in (50 // 8, 59 // 8, 6, 7), e
