@@ -399,6 +399,26 @@ int pso_transpose_batched(int n, const void* descs, int max_r, int max_c, void* 
  *   max_items >= max Rp*Cp/4. */
 int pso_lora_pack(int n, const void* descs, long max_items, float scale, void* stream);
 int pso_lora_grad_fold(int n, const void* descs, long max_items, void* stream);
+/* DoRA (csrc/dora.hip; peft 0.11 DoraLinearLayer): y = g . z (+ bias) (+ resid) around the LoRA projection z, with
+ * g_j = m_j / n_j, n_j = || W_j + s (B A)_j ||_2 taken as a constant in the backward, m the trained magnitude.  fp32
+ * arithmetic, no float atomics, fixed reduction orders (two runs give the same bits), no epsilon in m / n (as peft).
+ * pso_dora_weight_norm: descs = device array of n 72-B records {const elem* W; const float* A; const float* B;
+ *   float* m; float* n; float* g; long ldw; int out, in, r; float s;}: W [out][in] 16-bit with row stride ldw (8-B
+ *   aligned rows), A [r][in] fp32 (16-B aligned, in % 4 == 0) and B [out][r] fp32 (any 4-B boundary) the masters in
+ *   peft's shapes, so every rank is read as it is.  Accumulates (W_ji + s sum_k B_jk A_ki)^2 per element, writes n and
+ *   g = m / n; init != 0 also writes m := n first (g == 1).  max_out >= every record's out.  One launch, no host
+ *   synchronisation, no allocation (hipGraph-capturable).
+ * pso_dora_scale_fwd: y[row] = g . z[row] (+ bias) (+ resid[row]) for row < rows_policy, z[row] (+ bias)
+ *   (+ resid[row]) for the rest (the adapter-free reference half of a paired pass); rounded to the element type once.
+ * pso_dora_bwd: dy_g = ELEM(g . dy) out of place, and dm_j += (1 / n_j) sum_rows dy[row, j] z[row, j] through
+ *   per-64-row partial sums in ws (pso_dora_bwd_ws_bytes), added in ascending row order.
+ * All row operands: N % 8 == 0, ld % 8 == 0, 16-B aligned (else PSO_ERR_ARG). */
+int pso_dora_weight_norm(int n, const void* descs, int max_out, int init, void* stream);
+int pso_dora_scale_fwd(int M, int N, int rows_policy, const void* z, long ldz, const float* g, const void* bias,
+                       const void* resid, long ldr, void* y, long ldy, void* stream);
+size_t pso_dora_bwd_ws_bytes(int M, int N);
+int pso_dora_bwd(int M, int N, const void* dy, long lddy, const void* z, long ldz, const float* g, const float* n,
+                 void* dyg, long lddyg, float* dm, void* ws, size_t ws_bytes, void* stream);
 /* many transposes in one launch over a flat grid of 64 x 64 tiles: descs = device array of n 48-B records
  * {const bf16* src; bf16* dst; long ldi, ldo; int R, C, tiles_c, tile0;} (src [R][C] -> dst [C][R], tiles_c =
  * ceil(C / 64), tile0 = the record's first tile, ascending from 0), total_tiles = sum of ceil(R/64) * tiles_c. */

@@ -87,7 +87,7 @@ class DreamBoothPSOTrainer:
 
     @classmethod
     def from_args(cls, unet, vae, args, process_group=None, loss_scale=None, allow_prodigy=False,
-                  allow_lr_schedule=False):
+                  allow_lr_schedule=False, allow_dora=False):
         """Build from the reference script's argparse namespace (DB:parse_args).  Read: loss_type, beta_pso,
         neg_defactor, prior_loss_weight, distill_train_timesteps, learning_rate, adam_beta1 / adam_beta2 /
         adam_weight_decay / adam_epsilon, max_grad_norm, gradient_accumulation_steps, use_8bit_adam, mixed_precision,
@@ -99,7 +99,10 @@ class DreamBoothPSOTrainer:
         allow_lr_schedule=True lr_scheduler, lr_warmup_steps (script default 500), max_train_steps, lr_num_cycles and
         lr_power are read and the schedule is built (DB:1614-1621; the script's own defaults -- "constant" with a
         warm-up of 500 that the constant kind ignores -- give none); without it anything but "constant" with zero
-        warm-up raises ValueError as it always has;
+        warm-up raises ValueError as it always has.  And for --use_dora (DB:741): with allow_dora=True it is accepted
+        if and only if the UNet's adapter is a DoRA one (unet.lora.dora; add_adapter(cfg, allow_dora=True)) -- a
+        mismatch in either direction raises ValueError naming use_dora -- and without it use_dora raises as it always
+        has;
         a field the namespace does not carry counts as the script's default.  Flags that ask for training this
         trainer does not implement raise ValueError naming the flag (unet.check_lora_config's rule) instead of
         training something else.
@@ -134,8 +137,14 @@ class DreamBoothPSOTrainer:
                            prodigy_use_bias_correction=bool(get("prodigy_use_bias_correction", True)),
                            prodigy_safeguard_warmup=bool(get("prodigy_safeguard_warmup", True)))
         for flag in ("train_text_encoder", "with_prior_preservation", "use_dora"):
-            if get(flag, False):
+            if get(flag, False) and not (flag == "use_dora" and allow_dora):
                 raise ValueError(f"--{flag} is not implemented (the recipes under personalization/scripts leave it off)")
+        if allow_dora:
+            # the script hands use_dora to LoraConfig (DB:1321): the UNet's adapter must be the kind the flag names
+            want, have = bool(get("use_dora", False)), bool(getattr(unet.lora, "dora", False))
+            if want != have:
+                raise ValueError(f"--use_dora={want} but the UNet carries a {'DoRA' if have else 'plain LoRA'} adapter: "
+                                 "add it with LoraConfig(use_dora=args.use_dora) and add_adapter(..., allow_dora=True)")
         if not get("do_edm_style_training", False):
             raise ValueError("--do_edm_style_training is required: only the EDM-style epsilon training of the recipes "
                              "(DB:1787-1796) is implemented")

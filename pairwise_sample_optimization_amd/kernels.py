@@ -1323,6 +1323,76 @@ class LoraPadTable:
         check(lib().pso_lora_grad_fold(count, descs, size // 4, stream_ptr()), "pso_lora_grad_fold")
 
 
+class DoraNormTable:
+    """The DoRA row norms of every adapted projection in ONE launch (pso_dora_weight_norm): a fixed device table of
+    (W [out, in] 16-bit base weight rows, A [r, in], B [out, r] fp32 masters, s, m, n, g [out] fp32) records, built
+    once over persistent buffers.  `run()` writes n = ||W + s B A|| row-wise and g = m / n; `run(init=True)` also sets
+    m := n first (peft's initial magnitude: the adapter starts as plain LoRA)."""
+
+    RECORD = 72
+
+    def __init__(self, entries, device):
+        import numpy as np
+        dt = np.dtype([("W", "<u8"), ("A", "<u8"), ("B", "<u8"), ("m", "<u8"), ("n", "<u8"), ("g", "<u8"),
+                       ("ldw", "<i8"), ("out", "<i4"), ("in", "<i4"), ("r", "<i4"), ("s", "<f4")])
+        assert dt.itemsize == self.RECORD
+        arr = np.zeros(len(entries), dtype=dt)
+        self.max_out = 0
+        for i, (W, A, B, s, m, n, g) in enumerate(entries):
+            require_cuda(W, A, B, m, n, g)
+            out, fin = W.shape
+            r = A.shape[0]
+            assert W.dtype == ELEM and W.stride(1) == 1 and W.stride(0) % 4 == 0 and W.data_ptr() % 8 == 0 \
+                and fin % 4 == 0, "DoRA base weights need 8-byte aligned rows"
+            assert A.dtype == torch.float32 and A.is_contiguous() and A.shape == (r, fin) and A.data_ptr() % 16 == 0, \
+                "DoRA reads lora_A as contiguous fp32 [r, in] at a 16-byte boundary"
+            assert B.dtype == torch.float32 and B.is_contiguous() and B.shape == (out, r)
+            for v in (m, n, g):
+                assert v.dtype == torch.float32 and v.is_contiguous() and v.shape == (out,)
+            arr[i] = (W.data_ptr(), A.data_ptr(), B.data_ptr(), m.data_ptr(), n.data_ptr(), g.data_ptr(),
+                      W.stride(0), out, fin, r, float(s))
+            self.max_out = max(self.max_out, out)
+        self.n = len(entries)
+        self.keep = entries
+        self.desc = torch.from_numpy(arr.view(np.uint8)).to(device)
+
+    def run(self, init=False):
+        check(lib().pso_dora_weight_norm(self.n, self.desc.data_ptr(), self.max_out, int(bool(init)), stream_ptr()),
+              "pso_dora_weight_norm")
+
+
+def dora_scale_fwd(z, g, bias=None, resid=None, rows_policy=None, out=None):
+    """y [M, N] = g * z (+ bias) (+ resid) on the first rows_policy rows (default: all), z (+ bias) (+ resid) on the
+    rest; fp32 arithmetic, one rounding (pso_dora_scale_fwd).  z / resid / out: row-strided views are fine."""
+    require_cuda(z, g, bias, resid, out)
+    M, N = z.shape
+    y = torch.empty((M, N), device=z.device, dtype=ELEM) if out is None else out
+    assert z.dtype == ELEM and y.dtype == ELEM and g.dtype == torch.float32 and g.numel() == N and g.is_contiguous()
+    assert bias is None or (bias.dtype == ELEM and bias.numel() == N and bias.is_contiguous())
+    assert resid is None or (resid.dtype == ELEM and resid.shape == z.shape)
+    rp = M if rows_policy is None else int(rows_policy)
+    check(lib().pso_dora_scale_fwd(M, N, rp, ptr(z), _row_stride(z), ptr(g), ptr(bias), ptr(resid),
+                                   _row_stride(resid) if resid is not None else 0, ptr(y), _row_stride(y),
+                                   stream_ptr()), "pso_dora_scale_fwd")
+    return y
+
+
+def dora_bwd(dy, z, g, n, dm, out=None):
+    """dy_g [M, N] = ELEM(g * dy) (returned; dy itself is left alone) and dm [N] f32 += (1 / n) * column sums of
+    dy * z, in a fixed two-stage order (pso_dora_bwd).  dy / z: row-strided views are fine."""
+    require_cuda(dy, z, g, n, dm, out)
+    M, N = dy.shape
+    dyg = torch.empty((M, N), device=dy.device, dtype=ELEM) if out is None else out
+    assert dy.dtype == ELEM and z.dtype == ELEM and dyg.dtype == ELEM and z.shape == dy.shape
+    for v in (g, n, dm):
+        assert v.dtype == torch.float32 and v.numel() == N and v.is_contiguous()
+    wsb = int(lib().pso_dora_bwd_ws_bytes(M, N))
+    ws = _stream_ws(wsb, dy.device)
+    check(lib().pso_dora_bwd(M, N, ptr(dy), _row_stride(dy), ptr(z), _row_stride(z), ptr(g), ptr(n), ptr(dyg),
+                             _row_stride(dyg), ptr(dm), ptr(ws), ws.numel(), stream_ptr()), "pso_dora_bwd")
+    return dyg
+
+
 def transpose_batched(x, out=None):
     """[Z, R, C] (rows contiguous) -> [Z, C, R] bf16 in one launch (a descriptor per matrix)."""
     Z, R, C = x.shape

@@ -16,7 +16,11 @@
   the scalar state block `prodigy_state` instead, and `pso_state.json` names the optimizer under the additive key
   `optimizer`; loading a checkpoint of the other optimizer raises `KeyError`.  A trainer with a learning-rate schedule
   writes its `state_dict()` under the additive key `lr_schedule`; the position in the schedule is `opt_step` and needs
-  no field of its own.  On load the trainer's own schedule wins: one that differs from the checkpoint's (or a
+  no field of its own.  A DoRA adapter (`LoraState.dora`) adds one `unet.<module>.lora_magnitude_vector.weight` per
+  module to the LoRA file (peft 0.11's key; the converters below leave it as it is, and the bare
+  `lora_magnitude_vector` of older peft releases loads too), and its moments lie in the flat optimizer buffers like
+  any other tensor's.  A file with magnitudes does not load into a plain-LoRA UNet, nor one without into a DoRA UNet:
+  both raise `ValueError` naming `lora_magnitude_vector`.  On load the trainer's own schedule wins: one that differs from the checkpoint's (or a
   checkpoint with a schedule into a trainer without) warns; a checkpoint without the key loads as before.
 """
 import json
@@ -31,7 +35,8 @@ OPT_NAME = "optimizer.safetensors"
 
 
 def peft_to_diffusers(sd):
-    """convert_state_dict_to_diffusers for a peft LoRA state dict: `.lora_A.` -> `.lora.down.`, `.lora_B.` -> `.lora.up.`"""
+    """convert_state_dict_to_diffusers for a peft LoRA state dict: `.lora_A.` -> `.lora.down.`, `.lora_B.` -> `.lora.up.`
+    (DoRA's `.lora_magnitude_vector.` keys pass through unchanged)"""
     out = {}
     for k, v in sd.items():
         out[k.replace(".lora_A.", ".lora.down.").replace(".lora_B.", ".lora.up.")] = v

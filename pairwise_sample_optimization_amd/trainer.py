@@ -246,6 +246,9 @@ def trainable_segments(unet):
     for name in st.adapter_names():
         for t in st.adapter_views(st.master, name):
             segs.append((t.storage_offset() - base, t.numel()))
+        if getattr(st, "dora", False):  # peft's lora_magnitude_vector: a parameter tensor of its own per module
+            t = st.magnitude_view(st.master, name)
+            segs.append((t.storage_offset() - base, t.numel()))
     return segs
 
 

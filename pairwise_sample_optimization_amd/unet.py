@@ -331,6 +331,7 @@ def _tn_stacked(fg, lins, dy, x):
 # LoRA state: flat fp32 masters + flat fp32 grads (the all-reduce bucket), bf16 working copies
 # ======================================================================================================================
 LORA_TARGETS = ("to_k", "to_q", "to_v", "to_out.0")  # T:342, D:365, DB:1324
+MAGNITUDE_KEY = "lora_magnitude_vector"  # peft's name of a DoRA module's magnitude (state-dict keys, unpinned)
 
 
 class LoraConfig:
@@ -350,12 +351,15 @@ class LoraConfig:
             setattr(self, k, v)
 
 
-def check_lora_config(cfg):
+def check_lora_config(cfg, allow_dora=False):
     """(r, lora_alpha) of a peft-style LoraConfig, after checking that it asks for the adapters the reference trains:
     LoRA (not DoRA / rsLoRA) on exactly to_q / to_k / to_v / to_out.0 of every attention, gaussian init, no dropout, no
     bias, no per-module rank / alpha patterns, no extra trained modules.  A field the object does not carry counts as
     the reference's value (namespace configs: SimpleNamespace(r=..., lora_alpha=...)); a field that differs raises
-    ValueError naming it -- the kernels would otherwise train other adapters than the config asks for."""
+    ValueError naming it -- the kernels would otherwise train other adapters than the config asks for.
+    allow_dora=True lets use_dora=True through (DB:741, DB:1321: the same adapters with a trained magnitude vector per
+    module, LoraState(dora=True)); without it use_dora=True raises as it always has, so a caller that relied on the
+    refusal keeps it."""
     def get(name, ref):
         return getattr(cfg, name, ref)
 
@@ -380,6 +384,8 @@ def check_lora_config(cfg):
               ("megatron_config", None, lambda v: v is None), ("loftq_config", {}, lambda v: not v))
     for name, ref, ok in checks:
         v = get(name, ref)
+        if name == "use_dora" and allow_dora and v is True:
+            continue
         if not ok(v):
             raise ValueError(f"LoraConfig.{name}={v!r} is not implemented (the reference uses {ref!r})")
     return r, alpha
@@ -401,10 +407,19 @@ class LoraState:
     are PADDED to r_pad = 8 with zero rows of A / zero columns of B: numerically the same adapter, on the rank-8
     kernels.  refresh() packs master -> work (pso_lora_pack); the backward's products land in grad_pad and are folded
     into grad per gradient unit (fold_grads, pso_lora_grad_fold).  r, scale = alpha / r and the init std 1 / r are the
-    logical rank's; for multiples of 8 r_pad == r, the layouts coincide and nothing of this runs."""
+    logical rank's; for multiples of 8 r_pad == r, the layouts coincide and nothing of this runs.
 
-    def __init__(self, blocks, r, alpha, device):
+    dora=True (peft use_dora, DoraLinearLayer): every adapted module also trains a magnitude vector m [out], and its
+    output is (m / n) . (x W^T + s x A^T B^T) with n = ||W + s B A|| row-wise, a constant of the backward.  The
+    magnitudes are five more segments per block after the ten above -- attn1.m_qkv [3C] m_o [C], attn2.m_q [C]
+    m_kv [2C] m_o [C] -- in both layouts (same sizes, so the keys match), hence in master and grad: the clip, the
+    all-reduce units, the optimizers, the loss scalers and the checkpoints carry them as they carry A and B.  n and
+    g = m / n are two fp32 buffers of their own that no optimizer sees, rewritten by refresh() from the masters and
+    the base weights (bind_base) in one pso_dora_weight_norm launch.  dora=False: nothing of this exists."""
+
+    def __init__(self, blocks, r, alpha, device, dora=False):
         self.r, self.alpha, self.scale = r, alpha, alpha / r
+        self.dora = bool(dora)
         # the rank the kernels see: 8 (16-byte rows of the 16-bit operands, the 8-wide K granule of the K-tail / skinny
         # / TN kernels) for r < 8, with zero rows of A and zero columns of B beyond r; r itself otherwise.  8 and not
         # 16: rank 8 already runs everywhere (plain TN launches instead of the rank-16 streaming kernel), and 16 would
@@ -422,6 +437,11 @@ class LoraState:
                                         ("attn2.B_o", C, k)):
                     segs[key] = (off, rows, cols)
                     off += rows * cols
+                if self.dora:  # the magnitude vectors, one element per output row of the stacks above
+                    for key, rows in (("attn1.m_qkv", 3 * C), ("attn1.m_o", C), ("attn2.m_q", C),
+                                      ("attn2.m_kv", 2 * C), ("attn2.m_o", C)):
+                        segs[key] = (off, rows, 1)
+                        off += rows
                 out[path] = segs
             return out, off
 
@@ -487,10 +507,105 @@ class LoraState:
                     self._fold_names.append(name)
             self._pack = K.LoraPadTable(pack, device, ELEM)
             self._fold = K.LoraPadTable(fold, device, torch.float32)
+        # DoRA: n = ||W + s B A|| and g = m / n of every magnitude, fp32, outside the trained buffers.  Their own
+        # layout: per width C first the k/v vectors of its blocks in block order (the width-batched text K/V scale
+        # reads them as one [n * 2C] vector), then per block q/k/v, out, cross q, cross out.
+        self._dora_table = None
+        self.dora_n = self.dora_g = None
+        if self.dora:
+            self._dora_off, off = {}, 0
+            self.kv_g = {}
+            for C, bl in by_c.items():
+                self.kv_g[C] = (off, len(bl) * 2 * C)
+                for path, C2, _ in blocks:
+                    if C2 == C:
+                        self._dora_off[path, "attn2.m_kv"] = off
+                        off += 2 * C
+            for path, C, _ in blocks:
+                for key, rows in (("attn1.m_qkv", 3 * C), ("attn1.m_o", C), ("attn2.m_q", C), ("attn2.m_o", C)):
+                    self._dora_off[path, key] = off
+                    off += rows
+            self.dora_n = torch.ones(off, device=device, dtype=torch.float32)
+            self.dora_g = torch.ones(off, device=device, dtype=torch.float32)
+            for path, C, _ in blocks:
+                ns = self.blk[path]
+                for short, key in (("qkv", "attn1.m_qkv"), ("o1", "attn1.m_o"), ("q2", "attn2.m_q"),
+                                   ("kv2", "attn2.m_kv"), ("o2", "attn2.m_o")):
+                    o, rows = self._dora_off[path, key], self.layout[path][key][1]
+                    setattr(ns, "g_" + short, self.dora_g[o:o + rows])
+                    setattr(ns, "n_" + short, self.dora_n[o:o + rows])
+                    setattr(ns, "dm_" + short, self.seg(self.grad, path, key).view(-1))
+            self.kv_g = {C: self.dora_g[o:o + k] for C, (o, k) in self.kv_g.items()}
 
     def seg(self, t, path, key, padded=False):
         off, rows, cols = (self.pad_layout if padded else self.layout)[path][key]
         return t[off:off + rows * cols].view(rows, cols)
+
+    @staticmethod
+    def _split_name(name):
+        """(block path, "attn1" | "attn2", "to_q" | "to_k" | "to_v" | "to_out.0") of an adapter module path."""
+        parts = name.rsplit(".", 3 if name.endswith(".to_out.0") else 2)
+        return parts[0], parts[1], "to_out.0" if name.endswith(".to_out.0") else parts[2]
+
+    def _magnitude_slot(self, name):
+        """(block path, magnitude segment key, first row, rows) of adapter `name`'s magnitude vector."""
+        if not self.dora:
+            raise ValueError("this adapter has no magnitude vectors: add it with LoraConfig(use_dora=True) and "
+                             "add_adapter(..., allow_dora=True)")
+        path, attn, mod = self._split_name(name)
+        if mod == "to_out.0":
+            key, j = attn + ".m_o", 0
+        elif attn == "attn1":
+            key, j = "attn1.m_qkv", ("to_q", "to_k", "to_v").index(mod)
+        elif mod == "to_q":
+            key, j = "attn2.m_q", 0
+        else:
+            key, j = "attn2.m_kv", ("to_k", "to_v").index(mod)
+        C = self.layout[path]["attn1.m_o"][1]
+        return path, key, j * C, C
+
+    def magnitude_view(self, t, name, padded=False):
+        """The magnitude vector m [out] of adapter `name` in the flat tensor t (master / grad; padded: the working
+        layout).  DoRA states only."""
+        path, key, row0, rows = self._magnitude_slot(name)
+        return self.seg(t, path, key, padded).view(-1)[row0:row0 + rows]
+
+    def norm_views(self, name):
+        """(n, g) [out] of adapter `name`: the detached row norm ||W + s B A|| and the column scale m / n as of the
+        last refresh()."""
+        path, key, row0, rows = self._magnitude_slot(name)
+        o = self._dora_off[path, key] + row0
+        return self.dora_n[o:o + rows], self.dora_g[o:o + rows]
+
+    def bind_base(self, weights):
+        """DoRA: {adapter module path: its base weight parameter [out, in]} -> the device descriptor table of the
+        row-norm kernel, one record per peft tensor.  The table holds the addresses of the parameters' storage, which
+        stays put while the model trains; called by add_adapter and again by UNet2DConditionModel.prepare(), which must
+        follow anything that moves the parameters (.to(), a dtype change): _norms() checks that before each launch."""
+        if not self.dora or self.master.device.type != "cuda":
+            return
+        entries = []
+        self._dora_bound = []
+        for name in self.adapter_names(layout_order=True):
+            A, B = self.adapter_views(self.master, name)
+            n, g = self.norm_views(name)
+            entries.append((weights[name].data, A, B, self.scale, self.magnitude_view(self.master, name), n, g))
+            self._dora_bound.append((name, weights[name], weights[name].data_ptr()))
+        self._dora_table = K.DoraNormTable(entries, self.master.device)
+
+    def _norms(self, init=False):
+        """One pso_dora_weight_norm launch, after checking (host side, no sync) that every bound base weight still
+        lives where the table says."""
+        for name, p, where in self._dora_bound:
+            if p.data_ptr() != where:
+                raise RuntimeError(f"DoRA: the base weight of {name} moved since the adapter was bound to it (a .to() "
+                                   "or dtype change after add_adapter): call unet.prepare() to rebind")
+        self._dora_table.run(init=init)
+
+    def init_magnitudes(self):
+        """m := n = ||W + s B A|| of the current masters (peft sets it where the adapter is created, with B = 0: the
+        base weight's row norms), so g == 1 and the adapter starts as plain LoRA."""
+        self._norms(init=True)
 
     def adapter_views(self, t, name, padded=False):
         """(A, B) of adapter `name` in the flat tensor t: peft's [r][in] / [out][r] in the logical layout (master,
@@ -553,6 +668,8 @@ class LoraState:
         for A, sB, bl in self.kv_stacks.values():
             torch.cat([L.A_kv2 for L in bl], 0, out=A)
             torch.cat([L.sB_kv2 for L in bl], 0, out=sB)
+        if self._dora_table is not None:  # DoRA: n and g = m / n from the updated masters (one launch)
+            self._norms()
 
     def grad_seg(self, path, key):
         """Where the backward's weight-gradient products of segment `key` accumulate: the flat gradient, or for r < 8
@@ -579,12 +696,15 @@ class LoraState:
             self._fold.fold(*rng)
 
     def state_dict_peft(self):
-        """{module_path.lora_A.weight, module_path.lora_B.weight} (get_peft_model_state_dict naming)."""
+        """{module_path.lora_A.weight, module_path.lora_B.weight} (get_peft_model_state_dict naming); a DoRA state
+        adds module_path.lora_magnitude_vector.weight (peft 0.11's DoraLinearLayer.weight, adapter name stripped)."""
         out = {}
         for name in self.adapter_names():
             A, B = self.adapter_views(self.master, name)
             out[f"{name}.lora_A.weight"] = A.detach().clone()
             out[f"{name}.lora_B.weight"] = B.detach().clone()
+            if self.dora:
+                out[f"{name}.{MAGNITUDE_KEY}.weight"] = self.magnitude_view(self.master, name).detach().clone()
         return out
 
     def grad_dict_peft(self):
@@ -593,13 +713,32 @@ class LoraState:
             A, B = self.adapter_views(self.grad, name)
             out[f"{name}.lora_A.weight"] = A
             out[f"{name}.lora_B.weight"] = B
+            if self.dora:
+                out[f"{name}.{MAGNITUDE_KEY}.weight"] = self.magnitude_view(self.grad, name)
         return out
 
     def load_peft(self, sd):
+        """Copy a peft-named state dict into the masters.  Magnitudes: `<module>.lora_magnitude_vector.weight`, or the
+        bare `<module>.lora_magnitude_vector` of peft releases before 0.11.  A dict with magnitudes does not load into
+        a plain-LoRA state, nor one without into a DoRA state: either raises ValueError."""
+        has = [k for k in sd if MAGNITUDE_KEY in k]
+        if has and not self.dora:
+            raise ValueError(f"the state dict holds DoRA magnitudes (e.g. {has[0]}), this adapter is plain LoRA: add "
+                             "it with LoraConfig(use_dora=True) and add_adapter(..., allow_dora=True)")
+        if self.dora:
+            mags = {}
+            for name in self.adapter_names():
+                k = f"{name}.{MAGNITUDE_KEY}"
+                v = sd.get(k + ".weight", sd.get(k))
+                if v is None:
+                    raise ValueError(f"this adapter is DoRA, the state dict has no {k}.weight (a plain-LoRA file?)")
+                mags[name] = v
         for name in self.adapter_names():
             A, B = self.adapter_views(self.master, name)
             A.copy_(sd[f"{name}.lora_A.weight"])
             B.copy_(sd[f"{name}.lora_B.weight"])
+            if self.dora:
+                self.magnitude_view(self.master, name).copy_(mags[name].reshape(-1))
         self.refresh()
 
 
@@ -650,6 +789,10 @@ class BasicTransformerBlock(nn.Module):
         lo = rt.lora_on
         L = rt.lora.blk[path] if lo else None
         r = rt.r
+        # DoRA: each adapted projection runs without its bias / residual epilogue to give z = x W^T + s x A^T B^T;
+        # pso_dora_scale_fwd then forms (m / n) . z + bias + resid on the policy rows (z + bias + resid on the
+        # reference half of a paired pass).  Never with the fp8 forward (_runtime), so the ok8 branches are off.
+        do = rt.dora
         # paired pass (policy images first, then their reference copies): the adapters act on the first Mp rows only
         Mp = M // 2 if rt.paired else M
         tr = Mp if rt.paired else 0
@@ -676,6 +819,9 @@ class BasicTransformerBlock(nn.Module):
                 qkv = K.gemm_fp8(K.quant_rows_fp8(n1), f8((id(self), "qkv"), a1m.w_qkv),
                                  a2=K.quant_rows_fp8(u_qkv), w2=f8((id(self), "sB_qkv"), L.sB_qkv, ver),
                                  tail_group_n=C, tail_rows=tr)
+            elif do:
+                z_qkv = _gemm_fwd(n1, a1m.w_qkv, a2=u_qkv, w2=L.sB_qkv, tail_group_n=C, tail_rows=tr)
+                qkv = K.dora_scale_fwd(z_qkv, L.g_qkv, rows_policy=Mp)
             else:
                 qkv = _gemm_fwd(n1, a1m.w_qkv, a2=u_qkv, w2=L.sB_qkv, tail_group_n=C, tail_rows=tr)
         elif ok8(3 * C, C, "qkv"):
@@ -691,6 +837,9 @@ class BasicTransformerBlock(nn.Module):
             if ok8(C, C, "out"):  # (diagnostic kind, not in the default FP8_KINDS: DESIGN §7 #8 table)
                 h1 = K.gemm_fp8(K.quant_rows_fp8(a1), f8((id(self), "o1"), o1.weight), a2=K.quant_rows_fp8(u_o1),
                                 w2=f8((id(self), "sB_o1"), L.sB_o1, ver), bias=o1.bias, resid=x, tail_rows=tr)
+            elif do:
+                z_o1 = _gemm_fwd(a1, o1.weight, a2=u_o1, w2=L.sB_o1, tail_rows=tr)
+                h1 = K.dora_scale_fwd(z_o1, L.g_o1, bias=o1.bias, resid=x, rows_policy=Mp)
             else:
                 h1 = _gemm_fwd(a1, o1.weight, bias=o1.bias, resid=x, a2=u_o1, w2=L.sB_o1, tail_rows=tr)
         elif ok8(C, C, "out"):
@@ -709,6 +858,9 @@ class BasicTransformerBlock(nn.Module):
             elif ok8(C, C, "q2"):
                 q2 = K.gemm_fp8(K.quant_rows_fp8(n2), f8((id(self), "q2"), a2m.to_q.weight),
                                 a2=K.quant_rows_fp8(u_q2), w2=f8((id(self), "sB_q2"), L.sB_q2, ver), tail_rows=tr)
+            elif do:
+                z_q2 = _gemm_fwd(n2, a2m.to_q.weight, a2=u_q2, w2=L.sB_q2, tail_rows=tr)
+                q2 = K.dora_scale_fwd(z_q2, L.g_q2, rows_policy=Mp)
             else:
                 q2 = _gemm_fwd(n2, a2m.to_q.weight, a2=u_q2, w2=L.sB_q2, tail_rows=tr)
         elif ok8(C, C, "q2"):
@@ -728,6 +880,9 @@ class BasicTransformerBlock(nn.Module):
             if ok8(C, C, "out"):
                 h2 = K.gemm_fp8(K.quant_rows_fp8(a2), f8((id(self), "o2"), o2.weight), a2=K.quant_rows_fp8(u_o2),
                                 w2=f8((id(self), "sB_o2"), L.sB_o2, ver), bias=o2.bias, resid=h1, tail_rows=tr)
+            elif do:
+                z_o2 = _gemm_fwd(a2, o2.weight, a2=u_o2, w2=L.sB_o2, tail_rows=tr)
+                h2 = K.dora_scale_fwd(z_o2, L.g_o2, bias=o2.bias, resid=h1, rows_policy=Mp)
             else:
                 h2 = _gemm_fwd(a2, o2.weight, bias=o2.bias, resid=h1, a2=u_o2, w2=L.sB_o2, tail_rows=tr)
         elif ok8(C, C, "out"):
@@ -753,6 +908,9 @@ class BasicTransformerBlock(nn.Module):
                       st3=pol(st3), f=f)
             if lo:
                 sv.update(u_qkv=u_qkv, u_o1=u_o1, u_q2=u_q2, u_kv2=u_kv2, u_o2=u_o2)
+            if do:  # the unscaled projections of the policy rows: dm = sum dy z / n
+                sv.update(z_qkv=pol(z_qkv), z_o1=pol(z_o1), z_q2=pol(z_q2), z_o2=pol(z_o2),
+                          z_kv2=rt.kv_z[C][:, j * 2 * C:(j + 1) * 2 * C])
             if rt.fg is not None:  # full-UNet grads: the ff.proj / ff.out inputs too
                 sv.update(n3=n3, gg=gg)
             rt.saved.append(sv)
@@ -769,6 +927,14 @@ class BasicTransformerBlock(nn.Module):
         L = st.blk[path] if lo else None
         g = (lambda k: st.grad_seg(path, k)) if lo else None
         a1m, a2m = self.attn1, self.attn2
+
+        def dora(dy, sv, site):
+            """DoRA: dy -> dy_g = (m / n) . dy for the unchanged LoRA lines below (dX, dA and dB are the LoRA backward
+            on dy_g), and the site's magnitude gradient += sum_rows dy z / n; plain LoRA: dy itself."""
+            if not rt.dora:
+                return dy
+            return K.dora_bwd(dy, sv["z_" + site], getattr(L, "g_" + site), getattr(L, "n_" + site),
+                              getattr(L, "dm_" + site))
         # --- FF ---
         fg = rt.fg
         df = K.gemm_geglu_bwd(dh3, self.ff.out.wt, sv["f"])  # interleaved d[h | gate]
@@ -799,11 +965,12 @@ class BasicTransformerBlock(nn.Module):
         # --- cross attention out-proj:  y = a W^T + (a A^T)(sB)^T ;  v = dy sB ; da = dy W + v A ---
         o2 = a2m.to_out[0]
         if lo:
-            v_o2 = K.gemm(dh2, L.sBt_o2)
-            da2 = K.gemm(dh2, o2.wt, a2=v_o2, w2=L.At_o2)
+            e2 = dora(dh2, sv, "o2")
+            v_o2 = K.gemm(e2, L.sBt_o2)
+            da2 = K.gemm(e2, o2.wt, a2=v_o2, w2=L.At_o2)
             a2s, uo2 = sv["a2"], sv["u_o2"]
-            rt.side.launch(lambda: (rt.dw(v_o2, a2s, g("attn2.A_o")), rt.dw(dh2, uo2, g("attn2.B_o"), st.scale)),
-                           v_o2, a2s, dh2, uo2)
+            rt.side.launch(lambda: (rt.dw(v_o2, a2s, g("attn2.A_o")), rt.dw(e2, uo2, g("attn2.B_o"), st.scale)),
+                           v_o2, a2s, e2, uo2)
         else:
             da2 = K.gemm(dh2, o2.wt)
         if fg is not None:
@@ -817,6 +984,7 @@ class BasicTransformerBlock(nn.Module):
                                     sv["lse2"], da2.view(B, S, C), a2m.heads, dk=dk3[..., :C], dv=dk3[..., C:])
         dq2 = dq2.view(M, C)
         if lo:
+            dq2, dkv2 = dora(dq2, sv, "q2"), dora(dkv2, sv, "kv2")
             v_q2 = K.gemm(dq2, L.sBt_q2)
             dn2 = K.gemm(dq2, a2m.to_q.wt, a2=v_q2, w2=L.At_q2)
             n2s, uq2, enc_, u_kv2 = sv["n2"], sv["u_q2"], rt.enc, sv["u_kv2"]
@@ -850,11 +1018,12 @@ class BasicTransformerBlock(nn.Module):
         # --- self attention ---
         o1 = a1m.to_out[0]
         if lo:
-            v_o1 = K.gemm(dh1, L.sBt_o1)
-            da1 = K.gemm(dh1, o1.wt, a2=v_o1, w2=L.At_o1)
+            e1 = dora(dh1, sv, "o1")
+            v_o1 = K.gemm(e1, L.sBt_o1)
+            da1 = K.gemm(e1, o1.wt, a2=v_o1, w2=L.At_o1)
             a1s, uo1 = sv["a1"], sv["u_o1"]
-            rt.side.launch(lambda: (rt.dw(v_o1, a1s, g("attn1.A_o")), rt.dw(dh1, uo1, g("attn1.B_o"), st.scale)),
-                           v_o1, a1s, dh1, uo1)
+            rt.side.launch(lambda: (rt.dw(v_o1, a1s, g("attn1.A_o")), rt.dw(e1, uo1, g("attn1.B_o"), st.scale)),
+                           v_o1, a1s, e1, uo1)
         else:
             da1 = K.gemm(dh1, o1.wt)
         if fg is not None:
@@ -865,6 +1034,7 @@ class BasicTransformerBlock(nn.Module):
         K.attention_bwd(q3[..., :C], q3[..., C:2 * C], q3[..., 2 * C:], sv["a1"].view(B, S, C), sv["lse1"],
                         da1.view(B, S, C), a1m.heads, dq=d3[..., :C], dk=d3[..., C:2 * C], dv=d3[..., 2 * C:])
         if lo:
+            dqkv = dora(dqkv, sv, "qkv")
             v_qkv = K.gemm_grouped_skinny(dqkv, L.sBt_qkv, 3)
             dn1 = K.gemm(dqkv, a1m.wt_qkv, a2=v_qkv, w2=L.At_qkv) if need_dx else None
             n1s, u_qkv = sv["n1"], sv["u_qkv"]
@@ -1238,18 +1408,37 @@ class UNet2DConditionModel(nn.Module):
             if isinstance(m, BasicTransformerBlock):
                 yield name, m
 
-    def add_adapter(self, lora_config):
+    def add_adapter(self, lora_config, allow_dora=False):
         """peft LoraConfig(r, lora_alpha, init_lora_weights='gaussian', target_modules=[to_k,to_q,to_v,to_out.0])
         (T:338-345, D:361-366, DB:1319-1325).  The kernels implement exactly that adapter set: every LoraConfig field
-        is checked (check_lora_config) and anything else raises instead of training other adapters than asked."""
-        r, alpha = check_lora_config(lora_config)
+        is checked (check_lora_config) and anything else raises instead of training other adapters than asked.
+        allow_dora=True accepts use_dora=True (DB:1321): the same adapters with a trained magnitude per module, set
+        here to the base weight's row norms (B = 0), so the model starts as the plain-LoRA one.  Not with the fp8
+        forward."""
+        r, alpha = check_lora_config(lora_config, allow_dora=allow_dora)
+        dora = getattr(lora_config, "use_dora", False) is True
+        if dora and self.fp8:
+            raise ValueError("use_dora with the fp8 forward is not implemented: the e4m3 K-tail has no column scale")
         blocks = [(name, blk.dim, blk.attn2.kv_dim) for name, blk in self._attn_modules()]
         dev = self.conv_in.weight.device
-        self.lora = LoraState(blocks, r, alpha, dev)
+        self.lora = LoraState(blocks, r, alpha, dev, dora=dora)
         if dev.type == "cuda":
+            self.lora.bind_base(self._adapted_weights())
             self.lora.init_gaussian(seed=getattr(lora_config, "seed", 0))
+            if dora:
+                self.lora.init_magnitudes()
         self._adapters_enabled = True
         return self.lora
+
+    def _adapted_weights(self):
+        """{adapter module path: base weight [out, in]} of every LoRA target, for the DoRA row norms."""
+        out = {}
+        for name, blk in self._attn_modules():
+            for a in ("attn1", "attn2"):
+                m = getattr(blk, a)
+                for mod, lin in (("to_q", m.to_q), ("to_k", m.to_k), ("to_v", m.to_v), ("to_out.0", m.to_out[0])):
+                    out[f"{name}.{a}.{mod}"] = lin.weight
+        return out
 
     def grad_units(self):
         """[(unit, [parameter names])] in the order backward_nhwc finishes them: conv_out / conv_norm_out, the up blocks
@@ -1338,6 +1527,7 @@ class UNet2DConditionModel(nn.Module):
             self._prepare_caches()
         self._prepared = True
         if self.lora is not None:
+            self.lora.bind_base(self._adapted_weights())  # (DoRA only: the row norms read the base weights)
             self.refresh_lora()
 
     def _prepare_caches(self):
@@ -1392,6 +1582,9 @@ class UNet2DConditionModel(nn.Module):
             _lib.require_bf16("the fp8 forward (enable_fp8_forward / DreamBooth fp8=)")
         if on and self.full is not None:
             raise ValueError("fp8 forward: LoRA training only (the full-UNet mode updates the base weights)")
+        if on and self.lora is not None and self.lora.dora:
+            raise ValueError("fp8 forward with use_dora adapters is not implemented: the e4m3 K-tail has no column "
+                             "scale")
         self.fp8 = bool(on)
         self._fp8_cache = {}
         return self
@@ -1431,6 +1624,10 @@ class UNet2DConditionModel(nn.Module):
             A, sB = self.lora.kv_stacks[C][:2]  # same block order as grp.W (both follow _attn_modules)
             u = K.gemm(rt.pol(enc), A)
             kv = _gemm_fwd(enc, grp.W, a2=u, w2=sB, tail_group_n=C, tail_rows=enc.shape[0] // 2 if rt.paired else 0)
+            if rt.dora:  # DoRA: the column scale of every block's k / v at once; z kept for the backward
+                rows = rt.pol(enc).shape[0]
+                rt.kv_z[C] = kv[:rows]
+                kv = K.dora_scale_fwd(kv, self.lora.kv_g[C], rows_policy=rows)
         else:
             u, kv = None, K.gemm(enc, grp.W)
         rt.kv_cache[C] = (kv, u)
@@ -1449,6 +1646,10 @@ class UNet2DConditionModel(nn.Module):
         rt.lora = self.lora
         rt.r = self.lora.r_pad if lora_on else 0  # the rank the kernels slice by (LoraState.r_pad)
         rt.fp8 = self._fp8_weight if self.fp8 else None
+        rt.dora = lora_on and self.lora.dora  # DoRA: the column scale m / n around every adapted projection
+        rt.kv_z = {}
+        if rt.dora and self.fp8:
+            raise ValueError("use_dora adapters with the fp8 forward are not implemented")
         return rt
 
     def _embed(self, timestep, time_ids, text_embeds, B, dev):
