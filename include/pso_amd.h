@@ -419,6 +419,18 @@ int pso_dora_scale_fwd(int M, int N, int rows_policy, const void* z, long ldz, c
 size_t pso_dora_bwd_ws_bytes(int M, int N);
 int pso_dora_bwd(int M, int N, const void* dy, long lddy, const void* z, long ldz, const float* g, const float* n,
                  void* dyg, long lddyg, float* dm, void* ws, size_t ws_bytes, void* stream);
+/* Merged-weight LoRA / DoRA inference (csrc/lora_merge.hip; diffusers fuse_lora, peft merge_and_unload):
+ *   O[j][i] = ELEM( g_j . ( W[j][i] + s . sum_k B[j][k] A[k][i] ) ), fp32 arithmetic, k ascending, ONE rounding; g null
+ *   (plain LoRA): no product.  A zero adapter term keeps W's bits.  No atomics: two runs give the same bits.
+ * descs = device array of n 72-B records {const elem* W; const float* A; const float* B; const float* g; elem* O;
+ *   long ldw, ldo; int out, in, r; float s;}: W [out][in] 16-bit base rows with row stride ldw, A [r][in] and
+ *   B [out][r] the fp32 masters in peft's shapes (every rank is read as it is), g [out] fp32 or null, O [out][in]
+ *   16-bit rows with row stride ldo (a row range of a stacked forward-layout buffer).  W is only read.
+ * host_descs = the same n records in host memory: every record is checked there BEFORE the launch (PSO_ERR_ARG):
+ *   out, in, r > 0, no null W / A / B / O, in % 4 == 0, W and O 8-B aligned with ld % 4 == 0 and ld >= in (8-B loads
+ *   and stores), A 16-B aligned (16-B loads), B and g 4-B aligned.  n <= 65535.  One launch, no host synchronisation,
+ *   no allocation (hipGraph-capturable). */
+int pso_lora_merge(int n, const void* descs, const void* host_descs, void* stream);
 /* many transposes in one launch over a flat grid of 64 x 64 tiles: descs = device array of n 48-B records
  * {const bf16* src; bf16* dst; long ldi, ldo; int R, C, tiles_c, tile0;} (src [R][C] -> dst [C][R], tiles_c =
  * ceil(C / 64), tile0 = the record's first tile, ascending from 0), total_tiles = sum of ceil(R/64) * tiles_c. */

@@ -150,6 +150,7 @@ SIGNATURES = {
     "pso_dora_scale_fwd": (ci, [ci, ci, ci, vp, cl, vp, vp, vp, cl, vp, cl, vp]),
     "pso_dora_bwd_ws_bytes": (csz, [ci, ci]),
     "pso_dora_bwd": (ci, [ci, ci, vp, cl, vp, cl, vp, vp, vp, cl, vp, vp, csz, vp]),
+    "pso_lora_merge": (ci, [ci, vp, vp, vp]),
     "pso_gather_rows": (ci, [cl, cl, vp, vp, vp, vp]),
     "pso_grad_clip_coef": (ci, [cl, vp, cf, cf, vp, vp, csz, vp]),
     "pso_adamw_step": (ci, [cl, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, vp, vp]),

@@ -1361,6 +1361,44 @@ class DoraNormTable:
               "pso_dora_weight_norm")
 
 
+class LoraMergeTable:
+    """The merged weights O = ELEM(g . (W + s B A)) of every adapted projection in ONE launch (pso_lora_merge): a fixed
+    device table of (W [out, in] 16-bit base rows, A [r, in], B [out, r] fp32 masters, s, g [out] fp32 or None,
+    O [out, in] 16-bit destination rows -- a row range of a forward-layout buffer) records, built once over persistent
+    buffers, with a host copy that the entry checks before each launch.  `run()` re-merges from the current masters."""
+
+    RECORD = 72
+    DTYPE = [("W", "<u8"), ("A", "<u8"), ("B", "<u8"), ("g", "<u8"), ("O", "<u8"), ("ldw", "<i8"), ("ldo", "<i8"),
+             ("out", "<i4"), ("in", "<i4"), ("r", "<i4"), ("s", "<f4")]
+
+    def __init__(self, entries, device):
+        import numpy as np
+        dt = np.dtype(self.DTYPE)
+        assert dt.itemsize == self.RECORD
+        arr = np.zeros(len(entries), dtype=dt)
+        for i, (W, A, B, s, g, O) in enumerate(entries):
+            require_cuda(W, A, B, g, O)
+            out, fin = W.shape
+            r = A.shape[0]
+            for t in (W, O):
+                assert t.dtype == ELEM and t.shape == (out, fin) and t.stride(1) == 1 and t.stride(0) % 4 == 0 \
+                    and t.data_ptr() % 8 == 0 and fin % 4 == 0, "merged LoRA weights need 8-byte aligned rows"
+            assert A.dtype == torch.float32 and A.is_contiguous() and A.shape == (r, fin) and A.data_ptr() % 16 == 0, \
+                "the merge reads lora_A as contiguous fp32 [r, in] at a 16-byte boundary"
+            assert B.dtype == torch.float32 and B.is_contiguous() and B.shape == (out, r)
+            assert g is None or (g.dtype == torch.float32 and g.is_contiguous() and g.shape == (out,))
+            arr[i] = (W.data_ptr(), A.data_ptr(), B.data_ptr(), 0 if g is None else g.data_ptr(), O.data_ptr(),
+                      W.stride(0), O.stride(0), out, fin, r, float(s))
+        self.n = len(entries)
+        self.keep = entries
+        self.host = arr  # the entry reads it before every launch: the argument checks
+        self.desc = torch.from_numpy(arr.view(np.uint8)).to(device)
+
+    def run(self):
+        check(lib().pso_lora_merge(self.n, self.desc.data_ptr(), self.host.ctypes.data, stream_ptr()),
+              "pso_lora_merge")
+
+
 def dora_scale_fwd(z, g, bias=None, resid=None, rows_policy=None, out=None):
     """y [M, N] = g * z (+ bias) (+ resid) on the first rows_policy rows (default: all), z (+ bias) (+ resid) on the
     rest; fp32 arithmetic, one rounding (pso_dora_scale_fwd).  z / resid / out: row-strided views are fine."""

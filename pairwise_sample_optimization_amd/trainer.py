@@ -465,8 +465,14 @@ class PSOTrainer:
                  bucket_mb=32.0, loss_scale=None, optimizer="adamw", prodigy_beta3=None, prodigy_decouple=True,
                  prodigy_use_bias_correction=False, prodigy_safeguard_warmup=False, prodigy_d0=1e-6,
                  prodigy_d_coef=1.0, prodigy_growth_rate=float("inf"), lr_scheduler="constant", lr_warmup_steps=0,
-                 max_train_steps=None, lr_num_cycles=1, lr_power=1.0):
+                 max_train_steps=None, lr_num_cycles=1, lr_power=1.0, fused_sampling=False):
         self.unet = unet
+        # fused_sampling: sample_pairs runs its forwards on merged weights W + s B A (unet.fuse_lora) and unfuses on
+        # exit.  The loss never reads the sampling-time log-probs -- policy and reference are both recomputed at
+        # train time -- so the training arithmetic is untouched.  Off (the default): nothing is built or launched.
+        self.fused_sampling = bool(fused_sampling)
+        if self.fused_sampling and getattr(unet, "lora", None) is None:
+            raise ValueError("fused_sampling merges a LoRA adapter into the sampling weights: this UNet carries none")
         # loss_scale: None (no scaling), a float (initial scale), an amp.LossScaler or an amp.DeviceLossScaler (state
         # on the device, no sync in the optimizer step): dynamic loss scaling with inf-skip for fp16 training.
         # Active under the f16 library only -- bf16 has fp32's exponent range.
@@ -562,7 +568,8 @@ class PSOTrainer:
         loss_scale (f16 library only): the scaler to train with instead of the default host amp.LossScaler(), e.g.
         an amp.DeviceLossScaler.
         train.{lr_scheduler, lr_warmup_steps, max_train_steps, lr_num_cycles, lr_power} are read when present (the
-        reference configs carry none: an absent lr_scheduler is "constant")."""
+        reference configs carry none: an absent lr_scheduler is "constant"), and so is train.fused_sampling
+        (absent: False)."""
         tr = config.train
         if tr.distilled_train_steps != config.sample.num_steps - 1:
             raise AssertionError("train.distilled_train_steps must equal sample.num_steps - 1 "
@@ -590,6 +597,7 @@ class PSOTrainer:
                    num_reward=num_reward, process_group=process_group, ref_unet=ref_unet, latent_dtype=latent_dtype,
                    use_8bit_adam=bool(getattr(tr, "use_8bit_adam", False)), loss_scale=loss_scale,
                    optimizer=getattr(tr, "optimizer", "adamw"),
+                   fused_sampling=bool(getattr(tr, "fused_sampling", False)),
                    **{k: getattr(tr, k) for k in PRODIGY_KEYS + LR_SCHEDULE_KEYS if hasattr(tr, k)})
 
     # ------------------------------------------------------------------------------------------------------------
@@ -608,7 +616,18 @@ class PSOTrainer:
     @torch.no_grad()
     def sample_pairs(self, enc, pooled, time_ids, h, generator=None, reward_fn=None, decode_fn=None):
         """enc [B,77,Dc] bf16, pooled [B,Dp], time_ids [B,6].  Returns a dict of NHWC buffer tensors.
-        Both trajectories of a prompt are sampled in ONE UNet batch (image order 2b + k)."""
+        Both trajectories of a prompt are sampled in ONE UNet batch (image order 2b + k).
+        fused_sampling: the forwards read merged weights; one merge per sampling phase that follows an optimizer step
+        (fuse_lora's version check), none otherwise."""
+        if not self.fused_sampling:
+            return self._sample_pairs(enc, pooled, time_ids, h, generator, reward_fn, decode_fn)
+        self.unet.fuse_lora()
+        try:
+            return self._sample_pairs(enc, pooled, time_ids, h, generator, reward_fn, decode_fn)
+        finally:
+            self.unet.unfuse_lora()
+
+    def _sample_pairs(self, enc, pooled, time_ids, h, generator=None, reward_fn=None, decode_fn=None):
         dev = enc.device
         B = enc.shape[0]
         n_img = 2 * B

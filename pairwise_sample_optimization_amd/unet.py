@@ -536,6 +536,12 @@ class LoraState:
                     setattr(ns, "n_" + short, self.dora_n[o:o + rows])
                     setattr(ns, "dm_" + short, self.seg(self.grad, path, key).view(-1))
             self.kv_g = {C: self.dora_g[o:o + k] for C, (o, k) in self.kv_g.items()}
+        # merged-weight inference (UNet2DConditionModel.fuse_lora): nothing exists until bind_merge is called
+        self._merge_table = None
+        self._merge_bound = []
+        self.merge_on = False      # refresh() re-merges while set
+        self.merge_scale = 1.0     # the lora_scale the table was built with
+        self.merge_version = -1    # the `version` the merged copies hold (-1: none, or recorded by a capture)
 
     def seg(self, t, path, key, padded=False):
         off, rows, cols = (self.pad_layout if padded else self.layout)[path][key]
@@ -601,6 +607,30 @@ class LoraState:
                 raise RuntimeError(f"DoRA: the base weight of {name} moved since the adapter was bound to it (a .to() "
                                    "or dtype change after add_adapter): call unet.prepare() to rebind")
         self._dora_table.run(init=init)
+
+    def bind_merge(self, weights, dests, lora_scale=1.0):
+        """Merged-weight inference: {adapter module path: base weight parameter [out, in]} and {path: destination rows
+        [out, in] of a forward-layout buffer} -> the device descriptor table of pso_lora_merge, one record per peft
+        module, reading the fp32 masters (and, DoRA, g = m / n as refresh() leaves it) at scale alpha / r x lora_scale.
+        Like bind_base it holds the parameters' addresses: prepare() rebinds, merge() checks."""
+        entries, self._merge_bound = [], []
+        for name in self.adapter_names(layout_order=True):
+            A, B = self.adapter_views(self.master, name)
+            g = self.norm_views(name)[1] if self.dora else None
+            entries.append((weights[name].data, A, B, self.scale * lora_scale, g, dests[name]))
+            self._merge_bound.append((name, weights[name], weights[name].data_ptr()))
+        self._merge_table = K.LoraMergeTable(entries, self.master.device)
+        self.merge_scale, self.merge_version = lora_scale, -1
+
+    def merge(self):
+        """One pso_lora_merge launch from the current masters, after the host-side check _norms() makes.  A merge that
+        a stream capture records has not run yet: its copies count as stale, as _fp8_weight's do."""
+        for name, p, where in self._merge_bound:
+            if p.data_ptr() != where:
+                raise RuntimeError(f"fuse_lora: the base weight of {name} moved since the merge was bound to it (a "
+                                   ".to() or dtype change after fuse_lora): call unet.prepare() to rebind")
+        self._merge_table.run()
+        self.merge_version = -1 if torch.cuda.is_current_stream_capturing() else getattr(self, "version", 0)
 
     def init_magnitudes(self):
         """m := n = ||W + s B A|| of the current masters (peft sets it where the adapter is created, with B = 0: the
@@ -670,6 +700,8 @@ class LoraState:
             torch.cat([L.sB_kv2 for L in bl], 0, out=sB)
         if self._dora_table is not None:  # DoRA: n and g = m / n from the updated masters (one launch)
             self._norms()
+        if self.merge_on:  # fuse_lora: the merged copies follow every master update (after g, which they read)
+            self.merge()
 
     def grad_seg(self, path, key):
         """Where the backward's weight-gradient products of segment `key` accumulate: the flat gradient, or for r < 8
@@ -793,6 +825,8 @@ class BasicTransformerBlock(nn.Module):
         # pso_dora_scale_fwd then forms (m / n) . z + bias + resid on the policy rows (z + bias + resid on the
         # reference half of a paired pass).  Never with the fp8 forward (_runtime), so the ok8 branches are off.
         do = rt.dora
+        # fuse_lora: this block's merged weights g . (W + s B A) in the adapter-free branches below (lo is off then)
+        Wm = rt.merged.blk[path] if rt.merged is not None else None
         # paired pass (policy images first, then their reference copies): the adapters act on the first Mp rows only
         Mp = M // 2 if rt.paired else M
         tr = Mp if rt.paired else 0
@@ -827,7 +861,7 @@ class BasicTransformerBlock(nn.Module):
         elif ok8(3 * C, C, "qkv"):
             qkv = K.gemm_fp8(K.quant_rows_fp8(n1), f8((id(self), "qkv"), a1m.w_qkv))
         else:
-            qkv = K.gemm(n1, a1m.w_qkv)
+            qkv = K.gemm(n1, Wm.qkv if Wm is not None else a1m.w_qkv)
         q3 = qkv.view(B, S, 3 * C)
         a1, lse1 = K.attention_fwd(q3[..., :C], q3[..., C:2 * C], q3[..., 2 * C:], a1m.heads)
         a1 = a1.view(M, C)
@@ -845,7 +879,7 @@ class BasicTransformerBlock(nn.Module):
         elif ok8(C, C, "out"):
             h1 = K.gemm_fp8(K.quant_rows_fp8(a1), f8((id(self), "o1"), o1.weight), bias=o1.bias, resid=x)
         else:
-            h1 = K.gemm(a1, o1.weight, bias=o1.bias, resid=x)
+            h1 = K.gemm(a1, Wm.o1 if Wm is not None else o1.weight, bias=o1.bias, resid=x)
         # --- cross attention over the 77 text tokens ---
         n2, st2 = K.layer_norm_fwd(h1, self.norm2.weight, self.norm2.bias, 1e-5)
         enc = rt.enc  # [B*77, Dc]
@@ -866,7 +900,7 @@ class BasicTransformerBlock(nn.Module):
         elif ok8(C, C, "q2"):
             q2 = K.gemm_fp8(K.quant_rows_fp8(n2), f8((id(self), "q2"), a2m.to_q.weight))
         else:
-            q2 = K.gemm(n2, a2m.to_q.weight)
+            q2 = K.gemm(n2, Wm.q2 if Wm is not None else a2m.to_q.weight)
         # K/V of the text tokens: this block's columns of the width-batched projection (UNet2DConditionModel.kv_text)
         kv_all, u_all = rt.kv_text(C)
         j = self._kv_slot
@@ -888,7 +922,7 @@ class BasicTransformerBlock(nn.Module):
         elif ok8(C, C, "out"):
             h2 = K.gemm_fp8(K.quant_rows_fp8(a2), f8((id(self), "o2"), o2.weight), bias=o2.bias, resid=h1)
         else:
-            h2 = K.gemm(a2, o2.weight, bias=o2.bias, resid=h1)
+            h2 = K.gemm(a2, Wm.o2 if Wm is not None else o2.weight, bias=o2.bias, resid=h1)
         # --- GEGLU feed-forward ---
         n3, st3 = K.layer_norm_fwd(h2, self.norm3.weight, self.norm3.bias, 1e-5)
         ff = self.ff
@@ -1337,6 +1371,8 @@ class UNet2DConditionModel(nn.Module):
         self.full = None  # FullGradState when every parameter is trained (C3 / C4)
         self.fp8 = False  # fp8 forward of the LayerNorm-fed projections (enable_fp8_forward, config 5)
         self._fp8_cache = {}
+        self.lora_fused = False  # fuse_lora(): inference passes read the merged weights g . (W + s B A)
+        self._merged = None      # their forward-layout buffers, kept across unfuse_lora() for the next fuse
         self._adapters_enabled = True
         self._prepared = False
         self.gradient_checkpointing = False
@@ -1422,6 +1458,7 @@ class UNet2DConditionModel(nn.Module):
         blocks = [(name, blk.dim, blk.attn2.kv_dim) for name, blk in self._attn_modules()]
         dev = self.conv_in.weight.device
         self.lora = LoraState(blocks, r, alpha, dev, dora=dora)
+        self.lora_fused, self._merged = False, None  # merged copies belong to the adapter they were made from
         if dev.type == "cuda":
             self.lora.bind_base(self._adapted_weights())
             self.lora.init_gaussian(seed=getattr(lora_config, "seed", 0))
@@ -1528,6 +1565,8 @@ class UNet2DConditionModel(nn.Module):
         self._prepared = True
         if self.lora is not None:
             self.lora.bind_base(self._adapted_weights())  # (DoRA only: the row norms read the base weights)
+            if self._merged is not None:  # fuse_lora: rebind too; the refresh below re-merges while fused
+                self._bind_merge(self.lora.merge_scale)
             self.refresh_lora()
 
     def _prepare_caches(self):
@@ -1585,8 +1624,91 @@ class UNet2DConditionModel(nn.Module):
         if on and self.lora is not None and self.lora.dora:
             raise ValueError("fp8 forward with use_dora adapters is not implemented: the e4m3 K-tail has no column "
                              "scale")
+        if on and self.lora_fused:
+            raise ValueError("fp8 forward while fuse_lora() is in effect is not implemented (the e4m3 weight cache is "
+                             "keyed by module, not by the weight it was quantised from): call unfuse_lora() first")
         self.fp8 = bool(on)
         self._fp8_cache = {}
+        return self
+
+    # ---------------- merged-weight inference (diffusers fuse_lora / unfuse_lora, peft merge_and_unload) ----------------
+    def _bind_merge(self, lora_scale):
+        """(Re)allocate the merged buffers where they are missing or the model moved, and (re)build the merge table:
+        per block Wf_qkv [3C][C] (q / k / v write its row thirds), Wf_o1, Wf_q2, Wf_o2 [C][C]; per width C
+        Wf_kv [n * 2C][Dc] in the row order of _kv_groups[C].W.  The destinations are the buffers the forward reads,
+        so no repacking pass exists."""
+        dev = self.conv_in.weight.device
+        m = self._merged
+        if m is None or m.device != dev:
+            new = lambda rows, cols: torch.empty((rows, cols), device=dev, dtype=ELEM)
+            m = SimpleNamespace(device=dev, blk={}, kv={C: new(*g.W.shape) for C, g in self._kv_groups.items()})
+            for name, blk in self._attn_modules():
+                C = blk.dim
+                m.blk[name] = SimpleNamespace(qkv=new(3 * C, C), o1=new(C, C), q2=new(C, C), o2=new(C, C))
+            self._merged = m
+        dests = {}
+        for name, blk in self._attn_modules():
+            C, b = blk.dim, m.blk[name]
+            kv = m.kv[C][blk._kv_slot * 2 * C:(blk._kv_slot + 1) * 2 * C]
+            for mod, rows in (("attn1.to_q", b.qkv[:C]), ("attn1.to_k", b.qkv[C:2 * C]), ("attn1.to_v", b.qkv[2 * C:]),
+                              ("attn1.to_out.0", b.o1), ("attn2.to_q", b.q2), ("attn2.to_k", kv[:C]),
+                              ("attn2.to_v", kv[C:]), ("attn2.to_out.0", b.o2)):
+                dests[f"{name}.{mod}"] = rows
+        m.dests = dests  # {adapter module path: its rows of the buffers above}
+        self.lora.bind_merge(self._adapted_weights(), dests, lora_scale)
+
+    def _merge(self, lora_scale):
+        """Merged copies of the current masters at `lora_scale`: builds buffers and table on first use, and launches
+        unless the copies already hold this adapter version at this scale (the rule _fp8_weight follows: under a
+        stream capture the merge is always recorded)."""
+        if self.lora is None:
+            raise ValueError("fuse_lora / merge_and_unload: this UNet carries no LoRA adapter (add_adapter; the "
+                             "full-UNet mode has nothing to merge)")
+        lora_scale = float(lora_scale)
+        st = self.lora
+        if st.dora and lora_scale != 1.0:
+            raise ValueError(f"lora_scale={lora_scale} with a DoRA adapter is not implemented: its column scale m / n "
+                             "is computed at the adapter's own scale")
+        if not self._prepared:
+            self.prepare()
+        if self._merged is None or st._merge_table is None or st.merge_scale != lora_scale:
+            self._bind_merge(lora_scale)
+        if st.merge_version != getattr(st, "version", 0) or torch.cuda.is_current_stream_capturing():
+            st.merge()
+
+    def fuse_lora(self, lora_scale=1.0):
+        """diffusers' fuse_lora: from here on a forward with save=False, paired_ref=False and the adapters enabled
+        reads merged weights ELEM(g . (W + lora_scale alpha / r . B A)) (pso_lora_merge, from the fp32 masters) through
+        the adapter-free branches, and launches nothing for the adapter.  The base parameters are not written; the
+        training paths (save=True, the paired pass, forward() under grad mode) and disable_adapters() keep their
+        bits; refresh() and prepare() re-merge, so the copies are never stale.  ~2 bytes per adapted weight element
+        (1.9 GB at SDXL).  Not with the fp8 forward, and DoRA at lora_scale 1 only."""
+        if self.fp8 and self.lora is not None:
+            raise ValueError("fuse_lora() with the fp8 forward is not implemented (the e4m3 weight cache is keyed by "
+                             "module, not by the weight it was quantised from): enable_fp8_forward(False) first")
+        self._merge(lora_scale)
+        self.lora.merge_on = True
+        self.lora_fused = True
+        return self
+
+    def unfuse_lora(self):
+        """Back to the adapter path.  Exact by construction (the base weights were never written); the merged buffers
+        stay for the next fuse_lora()."""
+        self.lora_fused = False
+        if self.lora is not None:
+            self.lora.merge_on = False
+        return self
+
+    def merge_and_unload(self):
+        """peft's merge_and_unload (permanent): the merged weights at scale 1 become the module parameters, the
+        adapter and the merged buffers are dropped, and the model is a plain UNet whose state_dict() /
+        save_pretrained() is the merged model."""
+        self._merge(1.0)
+        with torch.no_grad():
+            for name, p in self._adapted_weights().items():
+                p.data.copy_(self._merged.dests[name])
+        self.lora, self._merged, self.lora_fused = None, None, False
+        self.prepare()
         return self
 
     def _fp8_weight(self, key, w, version=0):
@@ -1629,7 +1751,7 @@ class UNet2DConditionModel(nn.Module):
                 rt.kv_z[C] = kv[:rows]
                 kv = K.dora_scale_fwd(kv, self.lora.kv_g[C], rows_policy=rows)
         else:
-            u, kv = None, K.gemm(enc, grp.W)
+            u, kv = None, K.gemm(enc, rt.merged.kv[C] if rt.merged is not None else grp.W)
         rt.kv_cache[C] = (kv, u)
         return kv, u
 
@@ -1648,6 +1770,7 @@ class UNet2DConditionModel(nn.Module):
         rt.fp8 = self._fp8_weight if self.fp8 else None
         rt.dora = lora_on and self.lora.dora  # DoRA: the column scale m / n around every adapted projection
         rt.kv_z = {}
+        rt.merged = None  # fuse_lora: the merged weights of this pass (forward_nhwc)
         if rt.dora and self.fp8:
             raise ValueError("use_dora adapters with the fp8 forward are not implemented")
         return rt
@@ -1685,7 +1808,12 @@ class UNet2DConditionModel(nn.Module):
         B = x.shape[0]
         lora_on = self.lora is not None and self._adapters_enabled
         encf = enc.to(ELEM).reshape(B * enc.shape[1], enc.shape[2]).contiguous()
-        rt = self._runtime(B, encf, save, lora_on)
+        # fuse_lora: an inference pass with the adapters on runs the adapter-free branches on the merged weights;
+        # save=True, the paired pass and disable_adapters() are what they are without it
+        fused = lora_on and self.lora_fused and not save and not paired_ref
+        rt = self._runtime(B, encf, save, lora_on and not fused)
+        if fused:
+            rt.merged = self._merged
         temb_all = self._embed(timestep, time_ids, text_embeds, B, x.device)
         tb = lambda m: temb_all[:, m._temb_off:m._temb_off + m.cout]
         # conv_in (C=4): im2col GEMM
