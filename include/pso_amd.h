@@ -661,6 +661,22 @@ int pso_prodigy_step_lr(long n, float* param, const float* grad, const float* p0
                         float* s, void* state, const float* lr_dev, float beta1, float beta2, float beta3, float eps,
                         float weight_decay, int flags, float d_coef, float growth_rate, float grad_scale,
                         const float* clip_coef, const void* amp_state, void* ws, size_t ws_bytes, void* stream);
+/* Exponential moving average of the flat fp32 trained buffer (ema.hip): diffusers' EMAModel, the --use_ema of its
+ * training scripts.  Parity with the package is unpinned (diffusers is not available here; tests/ema_ref.py restates the
+ * arithmetic below).  The decay is evaluated on the host in double (ema.py EMAModel.get_decay) and one_minus_decay =
+ * float(1 - decay) is the only scalar that travels: there is no device-side state and nothing is read back.
+ * pso_ema_step, per element, three separately rounded fp32 operations in the order of
+ * s_param.sub_(one_minus_decay * (s_param - param)), never contracted into an FMA:
+ *   t = shadow - param;  u = one_minus_decay * t;  shadow = shadow - u
+ *   one_minus_decay == 0 leaves the shadow's bits as they were (the arithmetic is still done: a -0, inf or nan
+ *   element follows the restatement); one_minus_decay == 1 gives s - (s - p), which is not always p.  param is only read.
+ * pso_ema_swap exchanges a and b in one pass (EMAModel.store / copy_to / restore without a third buffer); a swap moves
+ * bits, so two swaps restore both.
+ * Both: 64-bit indices (n may exceed 2^31), grid-stride loops; buffers that are both 16-B aligned take 16-B loads and
+ * stores with a scalar tail, others 4-B ones.  PSO_ERR_ARG before any launch: n <= 0, a null or not 4-B aligned buffer,
+ * one_minus_decay outside [0, 1] or not finite, a == b or overlapping ranges for the swap. */
+int pso_ema_step(long n, float* shadow, const float* param, float one_minus_decay, void* stream);
+int pso_ema_swap(long n, float* a, float* b, void* stream);
 int pso_preference(int P, int m, const float* rewards, const int64_t* reward_idx, int mode, float* pref,
                    void* stream);
 

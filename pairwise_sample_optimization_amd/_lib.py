@@ -180,6 +180,8 @@ SIGNATURES = {
     "pso_prodigy_ws_bytes": (csz, [cl]),
     "pso_prodigy_step": (ci, [cl, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, cf, ci, cf, cf, cf, vp, vp, vp, csz,
                               vp]),
+    "pso_ema_step": (ci, [cl, vp, vp, cf, vp]),
+    "pso_ema_swap": (ci, [cl, vp, vp, vp]),
     "pso_zero_f32": (ci, [cl, vp, vp]),
     "pso_preference": (ci, [ci, ci, vp, vp, ci, vp, vp]),
     "pso_nhwc_to_nchw": (ci, [ci, ci, cl, vp, vp, ci, vp]),

@@ -30,7 +30,8 @@ from . import _lib
 from . import kernels as K
 from .amp import DeviceLossScaler, LossScaler, make_scaler
 from .schedulers import EulerDiscreteScheduler, db_distill_timesteps
-from .trainer import LastLr, OptStep, init_lr_schedule, init_optimizer_state, lora_optimizer_step
+from .trainer import (EMA_ARG_KEYS, LastLr, OptStep, check_ema_live, init_ema, init_lr_schedule,
+                      init_optimizer_state, lora_optimizer_step)
 
 
 class DreamBoothPSOTrainer:
@@ -43,7 +44,8 @@ class DreamBoothPSOTrainer:
                  loss_scale=None, use_8bit_adam=False, optimizer="adamw", prodigy_beta3=None, prodigy_decouple=True,
                  prodigy_use_bias_correction=False, prodigy_safeguard_warmup=False, prodigy_d0=1e-6,
                  prodigy_d_coef=1.0, prodigy_growth_rate=float("inf"), lr_scheduler="constant", lr_warmup_steps=0,
-                 max_train_steps=None, lr_num_cycles=1, lr_power=1.0):
+                 max_train_steps=None, lr_num_cycles=1, lr_power=1.0, use_ema=False, ema_decay=0.9999,
+                 ema_min_decay=0.0, ema_update_after_step=0, ema_use_warmup=False, ema_inv_gamma=1.0, ema_power=2 / 3):
         """Defaults: DB argparse defaults (DB:636-674, 757-777) overridden by the recipe scripts/pso_dog.sh.
         loss_scale: None | float (initial scale) | amp.LossScaler | amp.DeviceLossScaler -- fp16 training under the
         f16 library, which refuses to train without one; the bf16 library takes none.  use_8bit_adam: the script's
@@ -52,7 +54,8 @@ class DreamBoothPSOTrainer:
         learning_rate around 1.0 and reads betas, adam_weight_decay and adam_epsilon as the diffusers script does.
         lr_scheduler / lr_warmup_steps / max_train_steps / lr_num_cycles / lr_power: the script's get_scheduler call
         (DB:1614-1621), stepped once per applied optimizer step (DB:1962-1963); "constant" builds no schedule
-        (self.lr_schedule is None) whatever lr_warmup_steps says, as diffusers' constant kind ignores it."""
+        (self.lr_schedule is None) whatever lr_warmup_steps says, as diffusers' constant kind ignores it.
+        use_ema / ema_*: diffusers' --use_ema with the EMAModel arguments, as in PSOTrainer; off, self.ema is None."""
         if loss_type not in ("pso", "pso_db"):
             raise ValueError(f"Unknown loss type {loss_type}")  # DB:1929
         self.scaler = make_scaler(loss_scale)
@@ -79,6 +82,8 @@ class DreamBoothPSOTrainer:
                              prodigy_safeguard_warmup=prodigy_safeguard_warmup, prodigy_d0=prodigy_d0,
                              prodigy_d_coef=prodigy_d_coef, prodigy_growth_rate=prodigy_growth_rate)
         init_lr_schedule(self, lr_scheduler, lr_warmup_steps, max_train_steps, lr_num_cycles, lr_power)
+        init_ema(self, unet, use_ema, ema_decay, ema_min_decay, ema_update_after_step, ema_use_warmup, ema_inv_gamma,
+                 ema_power)
         self.clip_buf = torch.zeros(2, device=st.master.device, dtype=torch.float32)
         self.opt_step = 0
         self.n_micro = 0
@@ -103,6 +108,8 @@ class DreamBoothPSOTrainer:
         if and only if the UNet's adapter is a DoRA one (unet.lora.dora; add_adapter(cfg, allow_dora=True)) -- a
         mismatch in either direction raises ValueError naming use_dora -- and without it use_dora raises as it always
         has;
+        use_ema and ema_decay / ema_min_decay / ema_update_after_step / ema_use_warmup / ema_inv_gamma / ema_power are
+        read when the namespace carries them (the reference script has no such flags: absent means no EMA);
         a field the namespace does not carry counts as the script's default.  Flags that ask for training this
         trainer does not implement raise ValueError naming the flag (unet.check_lora_config's rule) instead of
         training something else.
@@ -177,7 +184,8 @@ class DreamBoothPSOTrainer:
                    adam_weight_decay=get("adam_weight_decay", 1e-4), adam_epsilon=get("adam_epsilon", 1e-8),
                    max_grad_norm=get("max_grad_norm", 1.0),
                    gradient_accumulation_steps=get("gradient_accumulation_steps", 1), process_group=process_group,
-                   loss_scale=loss_scale, use_8bit_adam=use_8bit_adam, optimizer=optimizer, **prodigy, **schedule)
+                   loss_scale=loss_scale, use_8bit_adam=use_8bit_adam, optimizer=optimizer, **prodigy, **schedule,
+                   **{k: getattr(args, k) for k in EMA_ARG_KEYS if hasattr(args, k)})
 
     @property
     def loss_scale(self):
@@ -207,6 +215,7 @@ class DreamBoothPSOTrainer:
     def micro_step(self, pixel_values, prompt_embeds, pooled, time_ids, generator=None):
         """One DreamBooth PSO micro-step (DB:1720-1964).  prompt_embeds [B,77,D], pooled [B,Dp], time_ids [B,6] are
         the instance prompt's; both halves use them (DB:1804, 1816-1818).  Returns the loss (device scalar)."""
+        check_ema_live(self, "micro_step")
         inp = self.prepare_inputs(pixel_values, generator)
         enc = prompt_embeds.repeat(2, 1, 1)
         pl = pooled.repeat(2, 1)

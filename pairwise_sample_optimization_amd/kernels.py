@@ -1232,6 +1232,31 @@ def prodigy_step(param, grad, state, lr, betas, eps, weight_decay, beta3=None, d
                              stream_ptr()), fn)
 
 
+def _check_ema_pair(who, a, b):
+    require_cuda(a, b)
+    for t in (a, b):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.PsoLibError(f"{who}: both buffers must be contiguous float32 tensors")
+    if a.numel() != b.numel():
+        raise _lib.PsoLibError(f"{who}: sizes differ ({a.numel()} and {b.numel()})")
+
+
+def ema_step(shadow, param, one_minus_decay):
+    """shadow -= one_minus_decay * (shadow - param) on flat fp32 buffers (pso_ema_step: diffusers' EMAModel.step, three
+    separately rounded fp32 operations per element).  one_minus_decay: a Python float in [0, 1], passed as one
+    float32.  One launch, no read-back; param is only read."""
+    _check_ema_pair("ema_step", shadow, param)
+    check(lib().pso_ema_step(shadow.numel(), ptr(shadow), ptr(param), float(one_minus_decay), stream_ptr()),
+          "pso_ema_step")
+    return shadow
+
+
+def ema_swap(a, b):
+    """Exchange the contents of two flat fp32 buffers in one pass (pso_ema_swap); no third buffer."""
+    _check_ema_pair("ema_swap", a, b)
+    check(lib().pso_ema_swap(a.numel(), ptr(a), ptr(b), stream_ptr()), "pso_ema_swap")
+
+
 def zero_(x):
     check(lib().pso_zero_f32(x.numel(), ptr(x), stream_ptr()), "pso_zero_f32")
     return x

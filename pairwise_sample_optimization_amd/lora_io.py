@@ -22,6 +22,12 @@
   any other tensor's.  A file with magnitudes does not load into a plain-LoRA UNet, nor one without into a DoRA UNet:
   both raise `ValueError` naming `lora_magnitude_vector`.  On load the trainer's own schedule wins: one that differs from the checkpoint's (or a
   checkpoint with a schedule into a trainer without) warns; a checkpoint without the key loads as before.
+  A trainer with an EMA of its weights (`use_ema`, `ema.EMAModel`) writes the shadow as a LoRA file of its own,
+  `pytorch_lora_weights_ema.safetensors`, next to the live one -- the same key layout (magnitudes included under
+  DoRA), so `lora_state_dict(dir, weight_name=...)` + `load_lora_into_unet` load it like any adapter -- and the EMA's
+  scalars under the additive key `ema`; loading restores both, so a resumed run continues bit for bit.  A checkpoint
+  without `ema` into a trainer with one raises `KeyError`; one with `ema` into a trainer without loads the rest and
+  warns.
 """
 import json
 import os
@@ -31,6 +37,7 @@ import torch
 from safetensors.torch import load_file, save_file
 
 LORA_WEIGHT_NAME = "pytorch_lora_weights.safetensors"
+EMA_LORA_WEIGHT_NAME = "pytorch_lora_weights_ema.safetensors"
 OPT_NAME = "optimizer.safetensors"
 
 
@@ -85,8 +92,20 @@ def load_lora_into_unet(state_dict, network_alphas, unet):
     st.load_peft({k: v.to(dev, torch.float32) for k, v in sd.items()})
 
 
+def load_lora_weights(unet, input_dir, weight_name=LORA_WEIGHT_NAME):
+    """The pipeline's `load_lora_weights(dir, weight_name=...)` for this UNet: lora_state_dict + load_lora_into_unet.
+    weight_name=EMA_LORA_WEIGHT_NAME loads the averaged adapter that save_state writes for a trainer with use_ema."""
+    sd, alphas = lora_state_dict(input_dir, weight_name=weight_name)
+    load_lora_into_unet(sd, alphas, unet)
+
+
 def save_state(trainer, output_dir):
     unet = trainer.unet
+    ema = getattr(trainer, "ema", None)
+    if ema is not None:
+        if ema.swapped:
+            raise RuntimeError("save_state while the EMA weights are swapped in: restore() the live weights first")
+        save_lora_weights(output_dir, peft_to_diffusers(ema.state_dict_peft()), weight_name=EMA_LORA_WEIGHT_NAME)
     save_lora_weights(output_dir, peft_to_diffusers(get_peft_model_state_dict(unet)))
     a8 = getattr(trainer, "adam8", None)
     pro = getattr(trainer, "prodigy", None)
@@ -107,12 +126,28 @@ def save_state(trainer, output_dir):
         sched = getattr(trainer, "lr_schedule", None)
         if sched is not None:
             meta["lr_schedule"] = sched.state_dict()
+        if ema is not None:
+            meta["ema"] = ema.scalars()
         json.dump(meta, f)
 
 
 def load_state(trainer, input_dir):
+    with open(os.path.join(input_dir, "pso_state.json")) as f:
+        meta = json.load(f)
+    ema = getattr(trainer, "ema", None)
+    if ema is not None:
+        if "ema" not in meta:
+            raise KeyError("checkpoint holds no EMA state; this trainer averages its weights (use_ema=True)")
+        if ema.swapped:
+            raise RuntimeError("load_state while the EMA weights are swapped in: restore() the live weights first")
+    elif "ema" in meta:
+        warnings.warn("checkpoint was written with an EMA of the weights (use_ema); this trainer keeps none: "
+                      f"{EMA_LORA_WEIGHT_NAME} and the EMA counters are not loaded")
     sd, alphas = lora_state_dict(input_dir)
     load_lora_into_unet(sd, alphas, trainer.unet)
+    if ema is not None:
+        ema.load_peft(diffusers_to_peft(lora_state_dict(input_dir, weight_name=EMA_LORA_WEIGHT_NAME)[0]))
+        ema.load_scalars(meta["ema"])
     opt = load_file(os.path.join(input_dir, OPT_NAME))
     a8 = getattr(trainer, "adam8", None)
     pro = getattr(trainer, "prodigy", None)
@@ -150,8 +185,6 @@ def load_state(trainer, input_dir):
             raise KeyError("checkpoint holds 8-bit AdamW state; this trainer runs fp32 AdamW")
         trainer.exp_avg.copy_(opt["exp_avg"])
         trainer.exp_avg_sq.copy_(opt["exp_avg_sq"])
-    with open(os.path.join(input_dir, "pso_state.json")) as f:
-        meta = json.load(f)
     scaler = getattr(trainer, "scaler", None)
     if scaler is not None and "loss_scaler" in meta:
         scaler.load_state_dict(meta["loss_scaler"])

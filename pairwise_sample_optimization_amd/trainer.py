@@ -328,6 +328,32 @@ class LastLr:
         return sched.lr32(tr.opt_step - 1)
 
 
+# the EMA arguments both trainers take (train.use_ema / train.ema_* of a run config, use_ema / ema_* of the DreamBooth
+# namespace; diffusers' --use_ema and the EMAModel constructor)
+EMA_ARG_KEYS = ("use_ema", "ema_decay", "ema_min_decay", "ema_update_after_step", "ema_use_warmup", "ema_inv_gamma",
+                "ema_power")
+
+
+def init_ema(tr, unet, use_ema=False, ema_decay=0.9999, ema_min_decay=0.0, ema_update_after_step=0,
+             ema_use_warmup=False, ema_inv_gamma=1.0, ema_power=2 / 3):
+    """tr.ema: None (the default: nothing is allocated or launched), or -- use_ema -- the ema.EMAModel over
+    trainable(unet)'s flat master that the optimizer step updates once per call.  Every rank applies the same update to
+    identical masters: no collective."""
+    tr.ema = None
+    if use_ema:
+        from .ema import EMAModel
+        tr.ema = EMAModel(unet, decay=ema_decay, min_decay=ema_min_decay, update_after_step=ema_update_after_step,
+                          use_ema_warmup=ema_use_warmup, inv_gamma=ema_inv_gamma, power=ema_power)
+
+
+def check_ema_live(tr, what):
+    """Training on the averaged weights would silently corrupt the run: refuse while tr.ema's shadow is swapped in."""
+    ema = getattr(tr, "ema", None)
+    if ema is not None and ema.swapped:
+        raise RuntimeError(f"{what} while the EMA weights are swapped in (EMAModel.copy_to / average_parameters): "
+                           "restore() the live weights first")
+
+
 def normalize_optimizer(name):
     """'adamw' or 'prodigy' (case-insensitive, the DreamBooth script's --optimizer, DB:622-627)."""
     opt = str(name).lower()
@@ -389,6 +415,8 @@ def _amp_optimizer_step(tr, scaler, scale):
     else:
         zeroed = False
         K.adamw_step_amp(master, grad, tr.exp_avg, tr.exp_avg_sq, lr, tr.betas, tr.adam_eps, tr.wd, st)
+    if getattr(tr, "ema", None) is not None:  # once per call, skipped or not (lora_optimizer_step's docstring)
+        tr.ema.step()
     K.amp_update(st, scaler.growth_factor, scaler.backoff_factor, scaler.growth_interval)
     if not zeroed:
         K.zero_(grad)
@@ -402,7 +430,13 @@ def lora_optimizer_step(tr):
     opt_step, clip_buf, lr, betas, adam_eps, wd, max_grad_norm, pg and, when the last backward of the window already
     issued the bucketed all-reduce (tr.sync_armed), the GradBuckets to finish.  fp16 training: tr.scaler is an
     amp.LossScaler (the norm is read back, one sync) or an amp.DeviceLossScaler (_amp_optimizer_step: no read-back).
-    tr.lr_schedule (None = the fixed rate tr.lr): the step runs at lr_schedule.lr(k), k = the steps applied before it."""
+    tr.lr_schedule (None = the fixed rate tr.lr): the step runs at lr_schedule.lr(k), k = the steps applied before it.
+    tr.ema (None = off; init_ema): ema.EMAModel.step() once per call, after the optimizer kernel -- and the opposite of
+    the schedule's rule: the schedule counts APPLIED steps, so a step the loss scaler skips does not advance it, while
+    the EMA counts accumulation windows, so the call is made on the host scaler's early return for a non-finite
+    gradient and under the device scaler's skip as well, and the shadow then moves towards the unchanged master
+    (diffusers' scripts call ema.step under accelerator.sync_gradients whether or not the scaler skipped)."""
+    check_ema_live(tr, "optimizer_step")
     master, grad, refresh = trainable(tr.unet)
     if getattr(tr, "sync_armed", False):
         scale = tr.buckets.finish()
@@ -424,6 +458,8 @@ def lora_optimizer_step(tr):
         scaler.update(found_inf)
         if found_inf:
             K.zero_(grad)
+            if getattr(tr, "ema", None) is not None:  # the EMA counts windows, not applied steps
+                tr.ema.step()
             return
     tr.opt_step += 1
     # a schedule (DB:1614-1621, stepped at DB:1962-1963): this step runs at lr(opt_step - 1) -- the host knows the
@@ -449,6 +485,8 @@ def lora_optimizer_step(tr):
         zeroed = False
         K.adamw_step(master, grad, tr.exp_avg, tr.exp_avg_sq, lr, tr.betas, tr.adam_eps, tr.wd, tr.opt_step,
                      grad_scale=scale, clip=tr.clip_buf)
+    if getattr(tr, "ema", None) is not None:
+        tr.ema.step()
     if not zeroed:
         K.zero_(grad)
     refresh(cast=cast)
@@ -465,7 +503,9 @@ class PSOTrainer:
                  bucket_mb=32.0, loss_scale=None, optimizer="adamw", prodigy_beta3=None, prodigy_decouple=True,
                  prodigy_use_bias_correction=False, prodigy_safeguard_warmup=False, prodigy_d0=1e-6,
                  prodigy_d_coef=1.0, prodigy_growth_rate=float("inf"), lr_scheduler="constant", lr_warmup_steps=0,
-                 max_train_steps=None, lr_num_cycles=1, lr_power=1.0, fused_sampling=False):
+                 max_train_steps=None, lr_num_cycles=1, lr_power=1.0, fused_sampling=False, use_ema=False,
+                 ema_decay=0.9999, ema_min_decay=0.0, ema_update_after_step=0, ema_use_warmup=False, ema_inv_gamma=1.0,
+                 ema_power=2 / 3):
         self.unet = unet
         # fused_sampling: sample_pairs runs its forwards on merged weights W + s B A (unet.fuse_lora) and unfuses on
         # exit.  The loss never reads the sampling-time log-probs -- policy and reference are both recomputed at
@@ -508,6 +548,10 @@ class PSOTrainer:
         # lr_scheduler / lr_warmup_steps / max_train_steps / lr_num_cycles / lr_power: diffusers' get_scheduler names
         # (DB:586-612); "constant" (the default) builds no schedule and the optimizer step is the fixed-rate one
         init_lr_schedule(self, lr_scheduler, lr_warmup_steps, max_train_steps, lr_num_cycles, lr_power)
+        # use_ema (diffusers' --use_ema) / ema_*: the EMAModel arguments; off (the default) self.ema is None and nothing
+        # is allocated or launched
+        init_ema(self, unet, use_ema, ema_decay, ema_min_decay, ema_update_after_step, ema_use_warmup, ema_inv_gamma,
+                 ema_power)
         self.opt_step = 0
         self.n_micro = 0
         self.clip_buf = torch.zeros(2, device=master.device, dtype=torch.float32)
@@ -569,7 +613,8 @@ class PSOTrainer:
         an amp.DeviceLossScaler.
         train.{lr_scheduler, lr_warmup_steps, max_train_steps, lr_num_cycles, lr_power} are read when present (the
         reference configs carry none: an absent lr_scheduler is "constant"), and so is train.fused_sampling
-        (absent: False)."""
+        (absent: False), and train.use_ema / train.ema_{decay, min_decay, update_after_step, use_warmup, inv_gamma,
+        power} (absent: no EMA)."""
         tr = config.train
         if tr.distilled_train_steps != config.sample.num_steps - 1:
             raise AssertionError("train.distilled_train_steps must equal sample.num_steps - 1 "
@@ -598,7 +643,7 @@ class PSOTrainer:
                    use_8bit_adam=bool(getattr(tr, "use_8bit_adam", False)), loss_scale=loss_scale,
                    optimizer=getattr(tr, "optimizer", "adamw"),
                    fused_sampling=bool(getattr(tr, "fused_sampling", False)),
-                   **{k: getattr(tr, k) for k in PRODIGY_KEYS + LR_SCHEDULE_KEYS if hasattr(tr, k)})
+                   **{k: getattr(tr, k) for k in PRODIGY_KEYS + LR_SCHEDULE_KEYS + EMA_ARG_KEYS if hasattr(tr, k)})
 
     # ------------------------------------------------------------------------------------------------------------
     # coefficients of transition j (host float32 scalars, the reference's operation order)
@@ -743,6 +788,7 @@ class PSOTrainer:
         the window end, T:857-861), so the batched pass produces the sum of the per-micro-step gradients: every
         pair's loss term keeps its weight 1 / (P * gas * T) (the per-micro-step mean over P pairs, divided by the
         accumulation count as accelerate does).  Larger batches keep the MFMA GEMMs fed (M = images * tokens)."""
+        check_ema_live(self, "micro_step")
         count = getattr(mb, "count", 1)
         if self.n_micro // self.gas_total != (self.n_micro + count - 1) // self.gas_total:
             raise ValueError("a batched pass must not cross an optimizer step")
