@@ -8,7 +8,8 @@ Architecture restated from diffusers 0.27.0 (environment.yml:15; called at T:775
 DP/sdxl_turbo_with_logprob.py:126-132): conv_in -> 3 down blocks (320/640/1280; transformer depth 0/2/10) -> mid
 (depth 10) -> 3 up blocks -> GroupNorm+SiLU -> conv_out; Timesteps(320)->MLP time embedding + the SDXL "text_time"
 added embedding; BasicTransformerBlock = LN/self-attn/LN/cross-attn(77x2048)/LN/GEGLU FF; LoRA (rank r, alpha r) on
-to_q/to_k/to_v/to_out.0 of all attentions (T:338-345).
+to_q/to_k/to_v/to_out.0 of all attentions (T:338-345).  Which kernel form each adapted projection takes (fp8, DoRA,
+merged, ...) is decided in ONE place, proj_form over the SITES table: DESIGN.md "Adapted projections".
 
 MI355X-first design:
   * activations channels-last bf16 ([tokens, C] / NHWC), fp32 statistics and accumulation;
@@ -244,7 +245,7 @@ _FULL_SIDE = os.environ.get("PSO_FULL_SIDE_STREAM", "1") == "1"
 # "tail": the LoRA up-projection as an e4m3 K-tail; "qkv" (the self-attention q/k/v) is off by default, see
 # enable_fp8_forward
 FP8_KINDS = {"q2", "ff", "tail"}
-FP8_MIN_TILES = int(os.environ.get("PSO_FP8_MIN_TILES", "192"))  # see BasicTransformerBlock.fwd (0: no occupancy rule)
+FP8_MIN_TILES = int(os.environ.get("PSO_FP8_MIN_TILES", "192"))  # see fp8_site_ok (0: no occupancy rule)
 # The e4m3 GEGLU form has 256 x 256 tiles only, while the bf16 one takes 256 x 320 tiles where they need fewer
 # tile-rounds (gemm.hip pso_gemm_geglu: rounds x tile width).  A round of e4m3 tiles costs ~1/1.3 of a bf16 one on
 # these shapes (the 2x MFMA rate less the row quantisation and the longer prologue: C5's GEGLU 5.7 -> 4.2 ms at equal
@@ -482,7 +483,7 @@ class LoraState:
             self.blk[path] = ns
         self._transposes = K.BatchedTranspose(pairs, device) if device.type == "cuda" else None
         # per width C: the k/v adapters of its blocks stacked in block order, A [n*2r, Dc] and sB [n*2C, r], for the
-        # width-batched text K/V projection (UNet2DConditionModel.kv_text); rebuilt by refresh()
+        # width-batched text K/V projection (_Runtime.kv_text); rebuilt by refresh()
         by_c = {}
         for path, C, Dc in blocks:
             by_c.setdefault(C, []).append(self.blk[path])
@@ -775,6 +776,108 @@ class LoraState:
 
 
 # ======================================================================================================================
+# adapted projections (DESIGN "Adapted projections"): the five sites, the form each takes, one forward / backward helper
+# ======================================================================================================================
+def _site(name, groups, fp8_kind, bf16_tail, grad):
+    """One adapted projection under LoraState's short name: its column groups (a LoRA pair each), its entry of
+    FP8_KINDS (None: never on e4m3), whether it has the "fp8 base, bf16 LoRA term" diagnostic form, its flat-gradient
+    keys (grad = "attn1.%s_qkv"), and the names of its fields in the per-block adapter namespace (LoraState.blk)."""
+    return SimpleNamespace(name=name, groups=groups, fp8_kind=fp8_kind, bf16_tail=bf16_tail, gA=grad % "A",
+                           gB=grad % "B", **{f: f"{f}_{name}" for f in ("A", "sB", "At", "sBt", "g", "n", "dm")})
+
+
+SITES = {s.name: s for s in (_site("qkv", 3, "qkv", True, "attn1.%s_qkv"), _site("o1", 1, "out", False, "attn1.%s_o"),
+                             _site("q2", 1, "q2", True, "attn2.%s_q"), _site("kv2", 2, None, False, "attn2.%s_kv"),
+                             _site("o2", 1, "out", False, "attn2.%s_o"))}
+_QKV, _O1, _Q2, _KV2, _O2 = SITES.values()
+_NO_MERGE = SimpleNamespace(qkv=None, o1=None, q2=None, o2=None)  # a block's merged weights outside fuse_lora
+
+
+def fp8_site_ok(fp8_on, kind, n_out, k_in, lora_on, r_pad, M):
+    """True when the [M, k_in] x [n_out, k_in]^T product of fp8 kind `kind` takes the e4m3 GEMM: fp8 forward on, kind
+    selected (FP8_KINDS, read at call time: tools and tests reassign it), a shape the kernel takes, 16-B rows of the
+    rank-r operands for the fp8 LoRA tail, and at least FP8_MIN_TILES 256 x 256 tiles over the FULL row count M -- by
+    default three quarters of a 256-CU round: below that the product is latency-bound, not MFMA-bound, and the separate
+    row quantisation makes it slower than bf16 (C5 at 1 + 1 images: the L2 cross q, 40 tiles, 28 vs 21 us)."""
+    return bool(fp8_on and kind in FP8_KINDS and n_out % 256 == 0 and k_in % 128 == 0 and
+                (not lora_on or r_pad % 16 == 0) and ((M + 255) // 256) * (n_out // 256) >= FP8_MIN_TILES)
+
+
+def proj_form(site, lora_on, dora, merged, ok8, tail_in_kinds):
+    """Which form the adapted projection `site` takes; the first match wins (ok8: fp8_site_ok of its product):
+      adapter on : ok8, the site has the diagnostic form, "tail" not in FP8_KINDS -> "fp8_base_bf16_tail"
+                   ok8 -> "fp8_tail" | DoRA -> "dora" | else "lora"
+      adapter off: ok8 -> "fp8" | merged weights present (fuse_lora) -> "merged" | else "plain"
+    kv2 has no fp8 kind, so never an fp8 form.  o1 / o2 have no bf16-tail form: they take the e4m3 tail even when
+    "tail" is not in FP8_KINDS -- what the code has always done ("out" is a diagnostic kind), kept as it is."""
+    s = SITES[site]
+    if ok8 and s.fp8_kind is not None:
+        return "fp8" if not lora_on else "fp8_base_bf16_tail" if s.bf16_tail and not tail_in_kinds else "fp8_tail"
+    if lora_on:
+        return "dora" if dora else "lora"
+    return "merged" if merged else "plain"
+
+
+def _proj_fwd(rt, L, s, x, w, wm=None, bias=None, resid=None, key=None, group_n=0):
+    """y = x W^T (+ the site's adapter on the policy rows) + bias + resid, in the form proj_form names.  L: the adapter
+    namespace (fields s.A / s.sB / s.g); wm: the merged weight of a fuse_lora pass; key: the owner of the e4m3 weight
+    copies (rt.fp8 cache keys (key, site) / (key, "sB_" + site)); group_n: columns per LoRA pair of a grouped K-tail.
+    Returns (y, u, z): u = pol(x) A^T for the backward (None: adapter off), z the unscaled projection (DoRA only)."""
+    lo, f8, M = rt.lora_on, rt.fp8, x.shape[0]
+    ok8 = f8 is not None and fp8_site_ok(True, s.fp8_kind, w.shape[0], w.shape[1], lo, rt.r, M)
+    form = proj_form(s.name, lo, rt.dora, wm is not None, ok8, "tail" in FP8_KINDS)
+    if form == "fp8":
+        return K.gemm_fp8(K.quant_rows_fp8(x), f8((key, s.name), w), bias=bias, resid=resid), None, None
+    if not lo:
+        return K.gemm(x, wm if form == "merged" else w, bias=bias, resid=resid), None, None
+    # paired pass (policy images first, then their reference copies): the adapter acts on the first Mp rows only
+    Mp, tr = (M // 2, M // 2) if rt.paired else (M, 0)
+    sB, u = getattr(L, s.sB), K.gemm(rt.pol(x), getattr(L, s.A))            # u [Mp, groups * r]
+    if form == "fp8_base_bf16_tail":  # diagnostics: the LoRA term in bf16, one product per column group
+        y = K.gemm_fp8(K.quant_rows_fp8(x), f8((key, s.name), w), bias=bias, resid=resid)
+        r, C = rt.r, w.shape[0] // s.groups
+        for j in range(s.groups):
+            sl = y[:Mp, j * C:(j + 1) * C]
+            sl.copy_(K.gemm(u[:, j * r:(j + 1) * r], sB[j * C:(j + 1) * C], resid=sl))
+        return y, u, None
+    if form == "fp8_tail":  # the sB copies follow the adapter version
+        return K.gemm_fp8(K.quant_rows_fp8(x), f8((key, s.name), w), a2=K.quant_rows_fp8(u),
+                          w2=f8((key, "sB_" + s.name), sB, rt.lora.version), tail_group_n=group_n, tail_rows=tr,
+                          bias=bias, resid=resid), u, None
+    if form == "dora":
+        # no bias / residual epilogue: z = x W^T + s x A^T B^T; pso_dora_scale_fwd then forms (m / n) . z + bias + resid
+        # on the policy rows (z + bias + resid on a paired pass's reference half).  Never with fp8 (_Runtime.__init__)
+        z = _gemm_fwd(x, w, a2=u, w2=sB, tail_group_n=group_n, tail_rows=tr)
+        return K.dora_scale_fwd(z, getattr(L, s.g), bias=bias, resid=resid, rows_policy=Mp), u, z
+    return _gemm_fwd(x, w, a2=u, w2=sB, tail_group_n=group_n, tail_rows=tr, bias=bias, resid=resid), u, None
+
+
+def _dora_bwd(rt, L, s, dy, sv):
+    """DoRA: dy -> dy_g = (m / n) . dy for the unchanged LoRA lines of the backward (dX, dA and dB are the LoRA backward
+    on dy_g), and the site's magnitude gradient += sum_rows dy z / n (z from the forward); plain LoRA: dy itself."""
+    if not rt.dora:
+        return dy
+    return K.dora_bwd(dy, sv["z_" + s.name], getattr(L, s.g), getattr(L, s.n), getattr(L, s.dm))
+
+
+def _proj_bwd(rt, L, s, g, dy, lin, sv, x):
+    """Backward of an ungrouped adapted projection y = x W^T + (x A^T)(sB)^T (the two out-projections):
+    v = dy sB ; dx = dy W + v A, the A / B weight-gradient products deferred on the side stream (g: key -> where they
+    accumulate); full-UNet mode: lin's own dW / db from the unscaled dy.  sv: what the block's forward saved."""
+    if rt.lora_on:
+        e = _dora_bwd(rt, L, s, dy, sv)
+        v = K.gemm(e, getattr(L, s.sBt))
+        dx = K.gemm(e, lin.wt, a2=v, w2=getattr(L, s.At))
+        u, scale = sv["u_" + s.name], rt.lora.scale
+        rt.side.launch(lambda: (rt.dw(v, x, g(s.gA)), rt.dw(e, u, g(s.gB), scale)), v, x, e, u)
+    else:
+        dx = K.gemm(dy, lin.wt)
+    if rt.fg is not None:
+        _lin_dw(rt.fg, lin, dy, x, rt)
+    return dx
+
+
+# ======================================================================================================================
 # blocks: fwd(x, rt) -> y (saving what bwd needs in a dict when rt.save) ; bwd(dy, saved, rt) -> dx
 # ======================================================================================================================
 class Attention(nn.Module):
@@ -818,90 +921,24 @@ class BasicTransformerBlock(nn.Module):
         C, M, B = self.dim, x.shape[0], rt.B
         S = M // B
         a1m, a2m = self.attn1, self.attn2
-        lo = rt.lora_on
+        lo, do, r, key = rt.lora_on, rt.dora, rt.r, id(self)
         L = rt.lora.blk[path] if lo else None
-        r = rt.r
-        # DoRA: each adapted projection runs without its bias / residual epilogue to give z = x W^T + s x A^T B^T;
-        # pso_dora_scale_fwd then forms (m / n) . z + bias + resid on the policy rows (z + bias + resid on the
-        # reference half of a paired pass).  Never with the fp8 forward (_runtime), so the ok8 branches are off.
-        do = rt.dora
-        # fuse_lora: this block's merged weights g . (W + s B A) in the adapter-free branches below (lo is off then)
-        Wm = rt.merged.blk[path] if rt.merged is not None else None
-        # paired pass (policy images first, then their reference copies): the adapters act on the first Mp rows only
-        Mp = M // 2 if rt.paired else M
-        tr = Mp if rt.paired else 0
-        pol = (lambda t: t[:t.shape[0] // 2]) if rt.paired else (lambda t: t)
+        # fuse_lora: this block's merged weights g . (W + s B A) for the adapter-free forms (lo is off then)
+        Wm = rt.merged.blk[path] if rt.merged is not None else _NO_MERGE
+        Mp, pol = (M // 2 if rt.paired else M), rt.pol  # paired pass: the policy rows (the adapters act on them only)
         # --- self attention: fused q/k/v projection, the three LoRA up-projections as a grouped K-tail ---
         n1, st1 = K.layer_norm_fwd(x, self.norm1.weight, self.norm1.bias, 1e-5)
-        f8 = rt.fp8  # fp8 forward (config 5): the LayerNorm-fed projections on e4m3 MFMA where the shapes allow
-        # (the fp8 LoRA tail reads 16-B rows of the rank-r operands: r % 16 == 0)
-        # ... and only where the e4m3 GEMM's 256 x 256 tiles make at least three quarters of a 256-CU round: below that
-        # the product is latency-bound, not MFMA-bound, and the separate row quantisation makes it slower than the bf16
-        # kernel (C5 at 1 + 1 images: the L2 cross-attention q, 2048 x 1280 -- 40 tiles -- 28 vs 21 us per launch)
-        ok8 = lambda n_out, k_in, kind: (f8 is not None and kind in FP8_KINDS and n_out % 256 == 0 and
-                                         k_in % 128 == 0 and (not lo or rt.r % 16 == 0) and
-                                         ((M + 255) // 256) * (n_out // 256) >= FP8_MIN_TILES)
-        ver = rt.lora.version if lo else 0
-        if lo:
-            u_qkv = K.gemm(pol(n1), L.A_qkv)                                # [Mp, 3r]
-            if ok8(3 * C, C, "qkv") and "tail" not in FP8_KINDS:  # diagnostics: the LoRA term in bf16
-                qkv = K.gemm_fp8(K.quant_rows_fp8(n1), f8((id(self), "qkv"), a1m.w_qkv))
-                for j in range(3):
-                    sl = qkv[:Mp, j * C:(j + 1) * C]
-                    sl.copy_(K.gemm(u_qkv[:, j * r:(j + 1) * r], L.sB_qkv[j * C:(j + 1) * C], resid=sl))
-            elif ok8(3 * C, C, "qkv"):
-                qkv = K.gemm_fp8(K.quant_rows_fp8(n1), f8((id(self), "qkv"), a1m.w_qkv),
-                                 a2=K.quant_rows_fp8(u_qkv), w2=f8((id(self), "sB_qkv"), L.sB_qkv, ver),
-                                 tail_group_n=C, tail_rows=tr)
-            elif do:
-                z_qkv = _gemm_fwd(n1, a1m.w_qkv, a2=u_qkv, w2=L.sB_qkv, tail_group_n=C, tail_rows=tr)
-                qkv = K.dora_scale_fwd(z_qkv, L.g_qkv, rows_policy=Mp)
-            else:
-                qkv = _gemm_fwd(n1, a1m.w_qkv, a2=u_qkv, w2=L.sB_qkv, tail_group_n=C, tail_rows=tr)
-        elif ok8(3 * C, C, "qkv"):
-            qkv = K.gemm_fp8(K.quant_rows_fp8(n1), f8((id(self), "qkv"), a1m.w_qkv))
-        else:
-            qkv = K.gemm(n1, Wm.qkv if Wm is not None else a1m.w_qkv)
+        qkv, u_qkv, z_qkv = _proj_fwd(rt, L, _QKV, n1, a1m.w_qkv, Wm.qkv, key=key, group_n=C)
         q3 = qkv.view(B, S, 3 * C)
         a1, lse1 = K.attention_fwd(q3[..., :C], q3[..., C:2 * C], q3[..., 2 * C:], a1m.heads)
         a1 = a1.view(M, C)
-        o1 = a1m.to_out[0]
-        if lo:
-            u_o1 = K.gemm(pol(a1), L.A_o1)
-            if ok8(C, C, "out"):  # (diagnostic kind, not in the default FP8_KINDS: DESIGN §7 #8 table)
-                h1 = K.gemm_fp8(K.quant_rows_fp8(a1), f8((id(self), "o1"), o1.weight), a2=K.quant_rows_fp8(u_o1),
-                                w2=f8((id(self), "sB_o1"), L.sB_o1, ver), bias=o1.bias, resid=x, tail_rows=tr)
-            elif do:
-                z_o1 = _gemm_fwd(a1, o1.weight, a2=u_o1, w2=L.sB_o1, tail_rows=tr)
-                h1 = K.dora_scale_fwd(z_o1, L.g_o1, bias=o1.bias, resid=x, rows_policy=Mp)
-            else:
-                h1 = _gemm_fwd(a1, o1.weight, bias=o1.bias, resid=x, a2=u_o1, w2=L.sB_o1, tail_rows=tr)
-        elif ok8(C, C, "out"):
-            h1 = K.gemm_fp8(K.quant_rows_fp8(a1), f8((id(self), "o1"), o1.weight), bias=o1.bias, resid=x)
-        else:
-            h1 = K.gemm(a1, Wm.o1 if Wm is not None else o1.weight, bias=o1.bias, resid=x)
+        o1 = a1m.to_out[0]  # ("out" is a diagnostic fp8 kind, not in the default FP8_KINDS: DESIGN §7 #8 table)
+        h1, u_o1, z_o1 = _proj_fwd(rt, L, _O1, a1, o1.weight, Wm.o1, o1.bias, x, key=key)
         # --- cross attention over the 77 text tokens ---
         n2, st2 = K.layer_norm_fwd(h1, self.norm2.weight, self.norm2.bias, 1e-5)
-        enc = rt.enc  # [B*77, Dc]
-        Se = enc.shape[0] // B
-        if lo:
-            u_q2 = K.gemm(pol(n2), L.A_q2)
-            if ok8(C, C, "q2") and "tail" not in FP8_KINDS:  # diagnostics: the LoRA term in bf16
-                q2 = K.gemm_fp8(K.quant_rows_fp8(n2), f8((id(self), "q2"), a2m.to_q.weight))
-                q2[:Mp].copy_(K.gemm(u_q2, L.sB_q2, resid=q2[:Mp]))
-            elif ok8(C, C, "q2"):
-                q2 = K.gemm_fp8(K.quant_rows_fp8(n2), f8((id(self), "q2"), a2m.to_q.weight),
-                                a2=K.quant_rows_fp8(u_q2), w2=f8((id(self), "sB_q2"), L.sB_q2, ver), tail_rows=tr)
-            elif do:
-                z_q2 = _gemm_fwd(n2, a2m.to_q.weight, a2=u_q2, w2=L.sB_q2, tail_rows=tr)
-                q2 = K.dora_scale_fwd(z_q2, L.g_q2, rows_policy=Mp)
-            else:
-                q2 = _gemm_fwd(n2, a2m.to_q.weight, a2=u_q2, w2=L.sB_q2, tail_rows=tr)
-        elif ok8(C, C, "q2"):
-            q2 = K.gemm_fp8(K.quant_rows_fp8(n2), f8((id(self), "q2"), a2m.to_q.weight))
-        else:
-            q2 = K.gemm(n2, Wm.q2 if Wm is not None else a2m.to_q.weight)
-        # K/V of the text tokens: this block's columns of the width-batched projection (UNet2DConditionModel.kv_text)
+        Se = rt.enc.shape[0] // B  # enc [B*77, Dc]
+        q2, u_q2, z_q2 = _proj_fwd(rt, L, _Q2, n2, a2m.to_q.weight, Wm.q2, key=key)
+        # K/V of the text tokens: this block's columns of the width-batched projection (_Runtime.kv_text)
         kv_all, u_all = rt.kv_text(C)
         j = self._kv_slot
         kv3 = kv_all.view(B, Se, -1)[..., j * 2 * C:(j + 1) * 2 * C]        # [B, 77, 2C] view
@@ -909,31 +946,18 @@ class BasicTransformerBlock(nn.Module):
         a2, lse2 = K.attention_fwd(q2.view(B, S, C), kv3[..., :C], kv3[..., C:], a2m.heads)
         a2 = a2.view(M, C)
         o2 = a2m.to_out[0]
-        if lo:
-            u_o2 = K.gemm(pol(a2), L.A_o2)
-            if ok8(C, C, "out"):
-                h2 = K.gemm_fp8(K.quant_rows_fp8(a2), f8((id(self), "o2"), o2.weight), a2=K.quant_rows_fp8(u_o2),
-                                w2=f8((id(self), "sB_o2"), L.sB_o2, ver), bias=o2.bias, resid=h1, tail_rows=tr)
-            elif do:
-                z_o2 = _gemm_fwd(a2, o2.weight, a2=u_o2, w2=L.sB_o2, tail_rows=tr)
-                h2 = K.dora_scale_fwd(z_o2, L.g_o2, bias=o2.bias, resid=h1, rows_policy=Mp)
-            else:
-                h2 = _gemm_fwd(a2, o2.weight, bias=o2.bias, resid=h1, a2=u_o2, w2=L.sB_o2, tail_rows=tr)
-        elif ok8(C, C, "out"):
-            h2 = K.gemm_fp8(K.quant_rows_fp8(a2), f8((id(self), "o2"), o2.weight), bias=o2.bias, resid=h1)
-        else:
-            h2 = K.gemm(a2, Wm.o2 if Wm is not None else o2.weight, bias=o2.bias, resid=h1)
-        # --- GEGLU feed-forward ---
+        h2, u_o2, z_o2 = _proj_fwd(rt, L, _O2, a2, o2.weight, Wm.o2, o2.bias, h1, key=key)
+        # --- GEGLU feed-forward (not adapted; fp8 forward: the e4m3 GEMM where fp8_site_ok allows) ---
         n3, st3 = K.layer_norm_fwd(h2, self.norm3.weight, self.norm3.bias, 1e-5)
-        ff = self.ff
-        f = torch.empty((Mp, ff.w_int.shape[0]), device=x.device, dtype=ELEM) if rt.save else None
-        if ok8(ff.w_int.shape[0], C, "ff") and fp8_geglu_pays(M, ff.w_int.shape[0]):
-            gg = K.gemm_fp8(K.quant_rows_fp8(n3), f8((id(self), "ff"), ff.w_int), bias=ff.b_int, geglu=True, out_pre=f,
+        ff, f8, Fi = self.ff, rt.fp8, self.ff.w_int.shape[0]
+        f = torch.empty((Mp, Fi), device=x.device, dtype=ELEM) if rt.save else None
+        if fp8_site_ok(f8 is not None, "ff", Fi, C, lo, r, M) and fp8_geglu_pays(M, Fi):
+            gg = K.gemm_fp8(K.quant_rows_fp8(n3), f8((key, "ff"), ff.w_int), bias=ff.b_int, geglu=True, out_pre=f,
                             pre_rows=Mp)
         else:
             gg = K.gemm_geglu(n3, ff.w_int, ff.b_int, out_pre=f, pre_rows=Mp)  # f: interleaved pre-activation (bwd)
-        if ok8(C, ff.out.weight.shape[1], "ffout"):  # ff.net.2 (diagnostic kind: DESIGN §7 #8 table)
-            h3 = K.gemm_fp8(K.quant_rows_fp8(gg), f8((id(self), "ffout"), ff.out.weight), bias=ff.out.bias, resid=h2)
+        if fp8_site_ok(f8 is not None, "ffout", C, ff.out.weight.shape[1], lo, r, M):  # ff.net.2 (diagnostic kind)
+            h3 = K.gemm_fp8(K.quant_rows_fp8(gg), f8((key, "ffout"), ff.out.weight), bias=ff.out.bias, resid=h2)
         else:
             h3 = K.gemm(gg, ff.out.weight, bias=ff.out.bias, resid=h2)
         if rt.save:  # the backward runs on the policy images only
@@ -951,26 +975,13 @@ class BasicTransformerBlock(nn.Module):
         return h3
 
     def bwd(self, dh3, sv, rt, path, need_dx=True):
-        C = self.dim
-        B = rt.B
-        M = dh3.shape[0]
+        C, B, M = self.dim, rt.B, dh3.shape[0]
         S = M // B
-        r = rt.r
-        lo = rt.lora_on
-        st = rt.lora
+        r, lo, st, fg = rt.r, rt.lora_on, rt.lora, rt.fg
         L = st.blk[path] if lo else None
         g = (lambda k: st.grad_seg(path, k)) if lo else None
         a1m, a2m = self.attn1, self.attn2
-
-        def dora(dy, sv, site):
-            """DoRA: dy -> dy_g = (m / n) . dy for the unchanged LoRA lines below (dX, dA and dB are the LoRA backward
-            on dy_g), and the site's magnitude gradient += sum_rows dy z / n; plain LoRA: dy itself."""
-            if not rt.dora:
-                return dy
-            return K.dora_bwd(dy, sv["z_" + site], getattr(L, "g_" + site), getattr(L, "n_" + site),
-                              getattr(L, "dm_" + site))
         # --- FF ---
-        fg = rt.fg
         df = K.gemm_geglu_bwd(dh3, self.ff.out.wt, sv["f"])  # interleaved d[h | gate]
         if fg is not None:
             _lin_dw(fg, self.ff.out, dh3, sv["gg"], rt)
@@ -997,18 +1008,7 @@ class BasicTransformerBlock(nn.Module):
                            h2s, dn3, st3)
         dh2 = K.layer_norm_bwd(sv["h2"], dn3, sv["st3"], self.norm3.weight, dadd=dh3)
         # --- cross attention out-proj:  y = a W^T + (a A^T)(sB)^T ;  v = dy sB ; da = dy W + v A ---
-        o2 = a2m.to_out[0]
-        if lo:
-            e2 = dora(dh2, sv, "o2")
-            v_o2 = K.gemm(e2, L.sBt_o2)
-            da2 = K.gemm(e2, o2.wt, a2=v_o2, w2=L.At_o2)
-            a2s, uo2 = sv["a2"], sv["u_o2"]
-            rt.side.launch(lambda: (rt.dw(v_o2, a2s, g("attn2.A_o")), rt.dw(e2, uo2, g("attn2.B_o"), st.scale)),
-                           v_o2, a2s, e2, uo2)
-        else:
-            da2 = K.gemm(dh2, o2.wt)
-        if fg is not None:
-            _lin_dw(fg, o2, dh2, sv["a2"], rt)
+        da2 = _proj_bwd(rt, L, _O2, g, dh2, a2m.to_out[0], sv, sv["a2"])
         enc = rt.enc
         Se = enc.shape[0] // B
         kv3 = sv["kv3"]
@@ -1018,7 +1018,7 @@ class BasicTransformerBlock(nn.Module):
                                     sv["lse2"], da2.view(B, S, C), a2m.heads, dk=dk3[..., :C], dv=dk3[..., C:])
         dq2 = dq2.view(M, C)
         if lo:
-            dq2, dkv2 = dora(dq2, sv, "q2"), dora(dkv2, sv, "kv2")
+            dq2, dkv2 = _dora_bwd(rt, L, _Q2, dq2, sv), _dora_bwd(rt, L, _KV2, dkv2, sv)
             v_q2 = K.gemm(dq2, L.sBt_q2)
             dn2 = K.gemm(dq2, a2m.to_q.wt, a2=v_q2, w2=L.At_q2)
             n2s, uq2, enc_, u_kv2 = sv["n2"], sv["u_q2"], rt.enc, sv["u_kv2"]
@@ -1050,25 +1050,14 @@ class BasicTransformerBlock(nn.Module):
             rt.side.launch(attn2_dw, dq2, n2, dkv2, enc, h1s, dn2, st2)
         dh1 = K.layer_norm_bwd(sv["h1"], dn2, sv["st2"], self.norm2.weight, dadd=dh2)
         # --- self attention ---
-        o1 = a1m.to_out[0]
-        if lo:
-            e1 = dora(dh1, sv, "o1")
-            v_o1 = K.gemm(e1, L.sBt_o1)
-            da1 = K.gemm(e1, o1.wt, a2=v_o1, w2=L.At_o1)
-            a1s, uo1 = sv["a1"], sv["u_o1"]
-            rt.side.launch(lambda: (rt.dw(v_o1, a1s, g("attn1.A_o")), rt.dw(e1, uo1, g("attn1.B_o"), st.scale)),
-                           v_o1, a1s, e1, uo1)
-        else:
-            da1 = K.gemm(dh1, o1.wt)
-        if fg is not None:
-            _lin_dw(fg, o1, dh1, sv["a1"], rt)
+        da1 = _proj_bwd(rt, L, _O1, g, dh1, a1m.to_out[0], sv, sv["a1"])
         q3 = sv["qkv"].view(B, S, 3 * C)
         dqkv = torch.empty((M, 3 * C), device=dh3.device, dtype=ELEM)
         d3 = dqkv.view(B, S, 3 * C)
         K.attention_bwd(q3[..., :C], q3[..., C:2 * C], q3[..., 2 * C:], sv["a1"].view(B, S, C), sv["lse1"],
                         da1.view(B, S, C), a1m.heads, dq=d3[..., :C], dk=d3[..., C:2 * C], dv=d3[..., 2 * C:])
         if lo:
-            dqkv = dora(dqkv, sv, "qkv")
+            dqkv = _dora_bwd(rt, L, _QKV, dqkv, sv)
             v_qkv = K.gemm_grouped_skinny(dqkv, L.sBt_qkv, 3)
             dn1 = K.gemm(dqkv, a1m.wt_qkv, a2=v_qkv, w2=L.At_qkv) if need_dx else None
             n1s, u_qkv = sv["n1"], sv["u_qkv"]
@@ -1302,6 +1291,59 @@ class TimestepEmbedding(nn.Module):
 # ======================================================================================================================
 class _Output(SimpleNamespace):
     pass
+
+
+class _Runtime:
+    """State of ONE forward_nhwc (and the backward_nhwc that may follow it): what the blocks' fwd / bwd read as `rt`."""
+
+    def __init__(self, unet, B, enc, save, lora_on):
+        self.unet = unet         # its _kv_groups: the width-batched text K/V weights
+        self.B = B               # images in the batch the blocks see: 2B inside the paired part of a paired pass
+        self.enc = enc           # text tokens [B*77, Dc] (paired part: duplicated; after the forward: the policy half)
+        self.save = save         # keep what the backward needs (off below the first adapter block)
+        self.saved = []          # the blocks' saved activations, popped by the backward in reverse order
+        self.lora_on = lora_on   # the adapters act in this pass (False: none, disabled, or a fuse_lora pass)
+        self.paired = False      # inside the [policy; reference] part of a paired pass
+        self.fg = unet.full if save else None  # FullGradState: every weight gradient is wanted
+        # full-UNet weight gradients run on the side stream beside the input-gradient GEMMs they do not feed (small-M
+        # dX and dW products each leave most CUs idle; GradBuckets joins it before each bucket's all-reduce)
+        self.side = K.SideStream(enabled=True) if (self.fg is not None and _FULL_SIDE) else K.SideStream()
+        self.lora = unet.lora    # LoraState or None
+        self.r = unet.lora.r_pad if lora_on else 0  # the rank the kernels slice by (LoraState.r_pad)
+        self.fp8 = unet._fp8_weight if unet.fp8 else None  # fp8 forward: (key, weight, version) -> its e4m3 copy
+        self.dora = lora_on and unet.lora.dora  # DoRA: the column scale m / n around every adapted projection
+        self.merged = None       # fuse_lora: the merged weights of this pass (forward_nhwc)
+        self.kv_cache = {}       # width C -> (text K/V of its blocks, their LoRA down-projection): kv_text
+        self.kv_z = {}           # DoRA: width C -> the unscaled text K/V of the policy rows
+        self.emb = None          # full-UNet mode: the embedding MLPs' activations (_embed_bwd)
+        self.cols_in = None      # full-UNet mode: conv_in's patch matrix (_conv_in_dw)
+        self.dtemb = None        # full-UNet backward: time_emb_proj output gradients [B, sum Co], fp32
+        self.dw = None           # backward: the LoRA weight-gradient product (TnRankQueue.add or K.gemm_tn)
+        self.unit_done = None    # set by the trainer: called with each gradient unit the backward completes
+        if self.dora and unet.fp8:
+            raise ValueError("use_dora adapters with the fp8 forward are not implemented")
+
+    def pol(self, t):
+        """The policy half of a paired pass's tensor (rows); the tensor itself otherwise."""
+        return t[:t.shape[0] // 2] if self.paired else t
+
+    def kv_text(self, C):
+        """K/V of the text tokens for every block of width C: ([rows, n*2C], LoRA down-projection [policy rows, n*2r]
+        or None), computed on first use in a pass (enc is then final: the paired duplication precedes every
+        transformer block).  Output column group j (C columns: k or v of block j // 2) takes the LoRA tail
+        u[:, j*r:(j+1)*r] (sB)^T -- the per-block grouped tail of the unbatched form, block after block."""
+        if C in self.kv_cache:
+            return self.kv_cache[C]
+        L = None
+        if self.lora_on:  # the stacks of the width: same block order as the weights (both follow _attn_modules)
+            A, sB = self.lora.kv_stacks[C][:2]
+            L = SimpleNamespace(A_kv2=A, sB_kv2=sB, g_kv2=self.lora.kv_g[C] if self.dora else None)
+        kv, u, z = _proj_fwd(self, L, _KV2, self.enc, self.unet._kv_groups[C].W,
+                             self.merged.kv[C] if self.merged is not None else None, group_n=C)
+        if z is not None:  # DoRA: the column scale of every block's k / v at once; z kept for the backward
+            self.kv_z[C] = z[:self.pol(self.enc).shape[0]]
+        self.kv_cache[C] = (kv, u)
+        return kv, u
 
 
 class UNet2DConditionModel(nn.Module):
@@ -1732,49 +1774,7 @@ class UNet2DConditionModel(nn.Module):
         self._fp8_cache[key] = (-1 if capturing else version, buf)
         return buf
 
-    def kv_text(self, rt, C):
-        """K/V of the text tokens for every block of width C: ([rows, n*2C], LoRA down-projection [policy rows, n*2r]
-        or None), computed on first use in a pass (rt.enc is then final: the paired duplication precedes every
-        transformer block).  Output column group j (C columns: k or v of block j // 2) takes the LoRA tail
-        u[:, j*r:(j+1)*r] (sB)^T -- the per-block grouped tail of the unbatched form, block after block."""
-        hit = rt.kv_cache.get(C)
-        if hit is not None:
-            return hit
-        grp = self._kv_groups[C]
-        enc = rt.enc
-        if rt.lora_on:
-            A, sB = self.lora.kv_stacks[C][:2]  # same block order as grp.W (both follow _attn_modules)
-            u = K.gemm(rt.pol(enc), A)
-            kv = _gemm_fwd(enc, grp.W, a2=u, w2=sB, tail_group_n=C, tail_rows=enc.shape[0] // 2 if rt.paired else 0)
-            if rt.dora:  # DoRA: the column scale of every block's k / v at once; z kept for the backward
-                rows = rt.pol(enc).shape[0]
-                rt.kv_z[C] = kv[:rows]
-                kv = K.dora_scale_fwd(kv, self.lora.kv_g[C], rows_policy=rows)
-        else:
-            u, kv = None, K.gemm(enc, rt.merged.kv[C] if rt.merged is not None else grp.W)
-        rt.kv_cache[C] = (kv, u)
-        return kv, u
-
     # ---------------- forward / backward ----------------
-    def _runtime(self, B, enc, save, lora_on):
-        fg = self.full if save else None
-        # full-UNet weight gradients run on the side stream beside the input-gradient GEMMs they do not feed (the
-        # small-M dX and dW products each leave most CUs idle; GradBuckets joins it before each bucket's all-reduce)
-        side = K.SideStream(enabled=True) if (fg is not None and _FULL_SIDE) else K.SideStream()
-        rt = SimpleNamespace(B=B, enc=enc, save=save, saved=[], lora_on=lora_on, paired=False, side=side, fg=fg)
-        rt.pol = lambda t: t[:t.shape[0] // 2] if rt.paired else t
-        rt.kv_cache = {}
-        rt.kv_text = lambda C: self.kv_text(rt, C)
-        rt.lora = self.lora
-        rt.r = self.lora.r_pad if lora_on else 0  # the rank the kernels slice by (LoraState.r_pad)
-        rt.fp8 = self._fp8_weight if self.fp8 else None
-        rt.dora = lora_on and self.lora.dora  # DoRA: the column scale m / n around every adapted projection
-        rt.kv_z = {}
-        rt.merged = None  # fuse_lora: the merged weights of this pass (forward_nhwc)
-        if rt.dora and self.fp8:
-            raise ValueError("use_dora adapters with the fp8 forward are not implemented")
-        return rt
-
     def _embed(self, timestep, time_ids, text_embeds, B, dev):
         cfg = self.cfg
         t = torch.as_tensor(timestep, device=dev).float().reshape(-1)
@@ -1811,7 +1811,7 @@ class UNet2DConditionModel(nn.Module):
         # fuse_lora: an inference pass with the adapters on runs the adapter-free branches on the merged weights;
         # save=True, the paired pass and disable_adapters() are what they are without it
         fused = lora_on and self.lora_fused and not save and not paired_ref
-        rt = self._runtime(B, encf, save, lora_on and not fused)
+        rt = _Runtime(self, B, encf, save, lora_on and not fused)
         if fused:
             rt.merged = self._merged
         temb_all = self._embed(timestep, time_ids, text_embeds, B, x.device)
@@ -1897,7 +1897,7 @@ class UNet2DConditionModel(nn.Module):
                                   accumulate=True)
         else:
             dh = K.group_norm_bwd(sv["h"], dhn, sv["st"], self.conv_norm_out.weight, self.conv_norm_out.bias, True)
-        unit_done = getattr(rt, "unit_done", None) or (lambda unit: None)  # overlapped gradient sync (GradBuckets)
+        unit_done = rt.unit_done or (lambda unit: None)  # overlapped gradient sync (GradBuckets)
         # LoRA weight gradients are deferred per gradient unit and issued as one batched launch per rank / orientation
         # (K.TnRankQueue) right before the unit is reported done -- its all-reduce bucket may be issued next
         dwq = K.TnRankQueue() if TN_BATCH else None
