@@ -377,10 +377,26 @@ class TnRankQueue:
         self.pending = {}
 
 
+def _nhwc_row_pitch(t, what, shape):
+    """The row pitch ld of an NHWC [B, Ho, Wo, Cout] tensor whose pixels are rows of one [B*Ho*Wo, ld] buffer (a dense
+    tensor: ld = Cout; a column slice of a wider buffer: ld > Cout).  Any other layout is an error, never a guess."""
+    _, Ho, Wo, Cout = shape
+    if t.shape != shape:
+        raise ValueError(f"conv2d: {what} has shape {tuple(t.shape)}, expected {shape}")
+    if t.is_contiguous():
+        return Cout
+    ld = t.stride(2)
+    if t.stride(3) != 1 or ld < Cout or t.stride(1) != Wo * ld or t.stride(0) != Ho * Wo * ld:
+        raise ValueError(f"conv2d: {what} with strides {tuple(t.stride())} is not a [B*Ho*Wo, ld >= Cout] row-pitched "
+                         f"view of shape {tuple(shape)}")
+    return ld
+
+
 def conv2d(x, weight, *, x2=None, mode=CONV_NORMAL, stride=1, pad=None, out_hw=None, bias=None, rowbias=None,
            resid=None, a2=None, w2=None, alpha=1.0, out=None, out_dtype=ELEM, accumulate=False):
     """NHWC implicit-GEMM conv.  x [B,H,W,C1] (+ x2 [B,H,W,C2] concatenated on channels); weight [Cout,ks,ks,C1+C2].
-    Returns [B,Ho,Wo,Cout]."""
+    Returns [B,Ho,Wo,Cout].  out / resid may be column slices of wider buffers (one row pitch >= Cout over all pixels);
+    any other strided layout raises ValueError before anything is launched."""
     require_cuda(x, weight)
     B, H, W, C1 = x.shape
     C2 = x2.shape[3] if x2 is not None else 0
@@ -399,8 +415,8 @@ def conv2d(x, weight, *, x2=None, mode=CONV_NORMAL, stride=1, pad=None, out_hw=N
     if out is None:
         out = torch.empty((B, Ho, Wo, Cout), device=x.device, dtype=out_dtype)
     K2 = a2.shape[1] if a2 is not None else 0
-    o2 = out.view(B * Ho * Wo, -1) if out.is_contiguous() else None
-    ldo = Cout if o2 is None else o2.stride(0)
+    ldo = _nhwc_row_pitch(out, "out", (B, Ho, Wo, Cout))
+    ldr = _nhwc_row_pitch(resid, "resid", (B, Ho, Wo, Cout)) if resid is not None else 0
     key = ("conv", B, Ho, Wo, Cout, ks * ks * Ct, K2)
     wsb = _GEMM_WS.get(key)
     if wsb is None:
@@ -409,7 +425,7 @@ def conv2d(x, weight, *, x2=None, mode=CONV_NORMAL, stride=1, pad=None, out_hw=N
             ptr(a2), _row_stride(a2) if a2 is not None else 0, K2,
             ptr(w2), _row_stride(w2) if w2 is not None else 0, float(alpha), ptr(bias),
             ptr(rowbias), rowbias.stride(0) if rowbias is not None else 0,
-            ptr(resid), Cout if resid is not None else 0, ptr(out), ldo, dtype_code(out), int(accumulate))
+            ptr(resid), ldr, ptr(out), ldo, dtype_code(out), int(accumulate))
     e0 = _prof_begin()
     if wsb:  # small output, long reduction (bs = 1 backward): deterministic split-K through a workspace
         ws = torch.empty(wsb, device=x.device, dtype=torch.uint8)

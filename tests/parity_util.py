@@ -11,6 +11,8 @@ contiguous output tensor cannot show a store that lands beside the slice it was 
   geglu_* / gemm_* cases, fp64 references and derived element-wise bounds of the GEMM epilogue tests
   group_norm_* / layer_norm_* / norm_*  fp64 references, rounding models, edge-weighted inputs and derived bounds of
                    the norm kernels, saved statistics and parameter gradients included
+  conv_*           cases, inputs inside NaN margins, the fp64 reference from torch's own operators with its derived
+                   element-wise bound, and a gather restatement (with plantable faults) of every convolution path
 
 Everything here runs on whatever device its inputs are on; tests/test_parity_util.py exercises it without a GPU.
 """
@@ -72,6 +74,11 @@ FILL_BITS = {2: 0x7FA5, 4: 0x7FA5A5A5}
 _IVIEW = {2: torch.int16, 4: torch.int32}
 
 
+def guarded_pitch(widths, gap=8):
+    """The row pitch (elements) of guarded()'s buffer."""
+    return -(-(gap + sum(w + gap for w in widths)) // 8) * 8
+
+
 def guarded(shape_rows, widths, gap=8, guard_rows=64, dtype=None, device=None):
     """One [shape_rows + guard_rows, ld] buffer whose rows are laid out [gap | w0 | gap | w1 | gap | ... | gap] (the
     last gap padded so that ld is a multiple of 8 elements), every element holding one fixed NaN-payload bit pattern.
@@ -83,8 +90,7 @@ def guarded(shape_rows, widths, gap=8, guard_rows=64, dtype=None, device=None):
         dtype = K.ELEM
     size = torch.empty((), dtype=dtype).element_size()
     fill, ivt = FILL_BITS[size], _IVIEW[size]
-    ld = gap + sum(w + gap for w in widths)
-    ld = -(-ld // 8) * 8
+    ld = guarded_pitch(widths, gap)
     rows = shape_rows + guard_rows
     buf = torch.empty((rows, ld), dtype=dtype, device=device)
     ibuf = buf.view(ivt)
@@ -107,6 +113,33 @@ def guarded(shape_rows, widths, gap=8, guard_rows=64, dtype=None, device=None):
                                  f"rows 0..{shape_rows - 1}, columns {spans}), bits {int(ibuf[r, col]) & (2 ** (8 * size) - 1):#x}")
 
     return views, check
+
+
+def guarded_flat(n, dtype=None, device=None, pad=4096):
+    """guarded() for an output that has to be dense (the direct small-Cout convolution needs ldo == Cout): one 1-D buffer
+    of pad + n + pad elements of the fill pattern.  Returns (view, check): the contiguous n-element view in its middle
+    (16-byte aligned: pad is a multiple of 8) and a closure asserting that head and tail kept the fill."""
+    if dtype is None:
+        from pairwise_sample_optimization_amd import kernels as K
+        dtype = K.ELEM
+    assert pad % 8 == 0
+    size = torch.empty((), dtype=dtype).element_size()
+    fill, ivt = FILL_BITS[size], _IVIEW[size]
+    buf = torch.empty(pad + n + pad, dtype=dtype, device=device)
+    ibuf = buf.view(ivt)
+    ibuf.fill_(fill)
+
+    def check(what="guard band"):
+        touched = ibuf != fill
+        touched[pad:pad + n] = False
+        if bool(touched.any()):
+            i = int(touched.nonzero()[0])
+            where = f"{pad - i} element(s) before the view" if i < pad else f"{i - pad - n} element(s) past its end"
+            raise AssertionError(f"{what}: {int(touched.sum())} element(s) outside the {n}-element view were written; "
+                                 f"first at {i} of the {pad + n + pad}-element buffer ({where}), bits "
+                                 f"{int(ibuf[i]) & (2 ** (8 * size) - 1):#x}")
+
+    return buf[pad:pad + n], check
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1110,3 +1143,361 @@ def run_ln_dparam_case(cuda, M, C, strided):
         cnt, msg = _vec_violations(outs[n], ref[n] + prevs[n].double(), bound)
         assert cnt == 0, f"{tag} {n}: {msg}"
         assert torch.equal(runs[0][n], runs[1][n]), f"{tag} {n}: a second call gave other bits"
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# convolutions: the implicit GEMM's gather (gemm.hip issue_tile / load_chunk_conv, gemm8p.hip CONV), conv_small.hip
+# ----------------------------------------------------------------------------------------------------------------------
+CONV_NORMAL, CONV_UP2, CONV_T2 = 1, 2, 3   # kernels.CONV_*; the third template argument of gemm_bf16_kernel
+
+
+def _tile(bm, bn, conv, wm=2, wn=2, pipe=False):
+    """launch()'s pso_note_kernel string of a 2-phase tile (gemm.hip)."""
+    return f"gemm_bf16_kernel<{bm}, {bn}, {conv}, {wm}, {wn}, 2, {'true' if pipe else 'false'}, 0>"
+
+
+_CONV8 = "gemm8p_kernel<0, true, false, false, 320, true>"
+
+
+def _cc(kind, B, H, W, C1, Cout, mode, kernel, variant=0, C2=0, ks=3, K2=0, out_hw=None, ws=False, ws_ks=0,
+        out="guarded"):
+    return dict(kind=kind, B=B, H=H, W=W, C1=C1, C2=C2, Cout=Cout, ks=ks, K2=K2, mode=mode, kernel=kernel,
+                variant=variant, out_hw=out_hw, ws=ws, ws_ks=ws_ks, out=out)
+
+
+# id -> geometry (kind, B, H, W of the INPUT, C1 (+ C2), Cout), epilogue mode, variant, kernel name
+#   kind:  "s1" stride 1, pad ks // 2; "s2" stride 2, pad 1; "s2asym" stride 2, pad 0, out_hw = (H // 2, W // 2) (the
+#          VAE downsample, vae.py); "up2" CONV_UP2; "t2" CONV_T2 with the input dy and out_hw the stride-2 conv's input
+#   mode:  "full" bias + rowbias + resid, 16-bit out; "bias" bias only, 16-bit out; "none" 16-bit out, no operand;
+#          "f32" fp32 out, no operand; "acc" fp32 accumulate over previous contents
+#   ws:    pso_conv2d_ws_bytes > 0, so kernels.conv2d hands pso_conv2d_ws a workspace; ws_ks: the K-splits the plan
+#          then takes (variant 52 declines the workspace it is handed: ws without ws_ks)
+#   out:   "guarded" a column slice of guarded() (ldo > Cout); "flat" guarded_flat() (ldo == Cout)
+# A 9 x 7 image is 63 pixels: 3 images are 189 rows, every 64-row tile holds two images and the last tile is ragged.
+# The stride-2 / asymmetric cases have M = 40 / 24 / 30 <= 64 rows at N = 128, where the dispatch takes the 64 x 128
+# tile (gemm_plan.h "if (f.M <= 64)"), not 64 x 64: the geometry is kept and the name says what runs.
+CONV_CASES = {
+    "s1-straddle": _cc("s1", 3, 9, 7, 64, 100, "full", _tile(64, 64, 1)),
+    "s1-f32": _cc("s1", 3, 9, 7, 64, 100, "f32", _tile(64, 64, 1)),
+    "s1-acc": _cc("s1", 3, 9, 7, 64, 100, "acc", _tile(64, 64, 1)),
+    "s1-tail": _cc("s1", 3, 9, 7, 64, 128, "full", _tile(64, 64, 1), K2=32),
+    "s1-concat": _cc("s1", 2, 9, 7, 64, 64, "full", _tile(64, 64, 1), C2=128),
+    "1x1": _cc("s1", 2, 9, 7, 128, 64, "bias", _tile(64, 64, 1), ks=1),
+    "s2-odd": _cc("s2", 2, 9, 7, 64, 128, "full", _tile(64, 128, 1)),
+    "s2-even": _cc("s2", 2, 8, 6, 64, 128, "bias", _tile(64, 128, 1)),
+    "s2asym-vae": _cc("s2asym", 2, 10, 6, 128, 128, "bias", _tile(64, 128, 1)),
+    "up2": _cc("up2", 2, 5, 3, 128, 64, "bias", _tile(64, 64, 2)),
+    "t2-odd": _cc("t2", 2, 5, 4, 128, 64, "f32", _tile(64, 64, 3), out_hw=(9, 7)),
+    "t2-even": _cc("t2", 2, 4, 3, 128, 64, "f32", _tile(64, 64, 3), out_hw=(8, 6)),
+    # 36 K-tiles -> two splits of 18, one 128 x 128 tile; the reduce kernel applies the epilogue once
+    "splitk": _cc("s1", 2, 9, 7, 256, 64, "full", _tile(128, 128, 1, 2, 4), ws=True, ws_ks=2),
+    "splitk-concat": _cc("s1", 2, 9, 7, 192, 64, "full", _tile(128, 128, 1, 2, 4), C2=64, ws=True, ws_ks=2),
+    "small-c1": _cc("s1", 2, 16, 32, 64, 1, "bias", "conv3x3_smallc_kernel<1, 0>", out="flat"),
+    "small-c2": _cc("s1", 2, 16, 32, 64, 2, "bias", "conv3x3_smallc_kernel<2, 0>", out="flat"),
+    "small-c3": _cc("s1", 2, 16, 32, 64, 3, "bias", "conv3x3_smallc_kernel<3, 0>", out="flat"),
+    "small-c3-128": _cc("s1", 2, 32, 16, 128, 3, "none", "conv3x3_smallc_kernel<3, 128>", out="flat"),
+    # ldo != Cout: must NOT take the direct kernel -- the N = 3 implicit GEMM
+    "small-strided-out": _cc("s1", 2, 16, 32, 64, 3, "bias", _tile(64, 64, 1)),
+    # knob-pinned forms (the tools build)
+    "8p-one-tile": _cc("s1", 1, 16, 16, 64, 320, "full", _CONV8, variant=44),
+    "8p-three-images": _cc("s1", 3, 16, 16, 64, 320, "full", _CONV8, variant=44),
+    "8p-wide": _cc("s1", 2, 8, 32, 128, 640, "full", _CONV8, variant=44),
+    "8p-tall": _cc("s1", 1, 32, 8, 64, 320, "full", _CONV8, variant=44),
+    "tile-256x256": _cc("s1", 3, 9, 7, 64, 320, "full", _tile(256, 256, 1, 2, 4), variant=4),
+    "tile-128x160": _cc("s1", 3, 9, 7, 64, 320, "full", _tile(128, 160, 1), variant=12),
+    "tile-128x128": _cc("s1", 3, 9, 7, 64, 320, "full", _tile(128, 128, 1, 2, 4), variant=8),
+    "tile-64x160": _cc("s1", 3, 9, 7, 64, 320, "full", _tile(64, 160, 1), variant=20),
+    "tile-128x128-pipe": _cc("s1", 3, 9, 7, 64, 320, "full", _tile(128, 128, 1, 2, 4, True), variant=11),
+    # the splitk shape and inputs with the split off: N = 64 -> the unsplit 64 x 64 tile, held to the same bound
+    "splitk-off": _cc("s1", 2, 9, 7, 256, 64, "full", _tile(64, 64, 1), variant=52, ws=True),
+}
+CONV_DEFAULT_IDS = [k for k, c in CONV_CASES.items() if c["variant"] == 0]
+CONV_KNOB_IDS = [k for k, c in CONV_CASES.items() if c["variant"] != 0]
+# Worst |conv_restatement - fp64| / bound over every id above, measured by tests/test_parity_util.py on the CPU (it
+# prints one line per id): bf16 0.970 ("1x1"), fp16 0.905 ("1x1"); the fp32-output ids stay below 0.002.  Close to 1 is
+# what the bound means: u_out is the unit roundoff of the output format, which the final rounding of a value just above
+# a power of two reaches; the (K + K2 + 8) 2^-23 term is what is left for the order of the fp32 sums.
+
+
+def conv_geom(case):
+    """(mode, stride, pad, Ho, Wo): the arguments kernels.conv2d is called with (T2 as unet.py calls it: stride and
+    pad at their defaults 1 and ks // 2, the target size through out_hw)."""
+    kind, H, W, ks = case["kind"], case["H"], case["W"], case["ks"]
+    if kind == "s1":
+        return CONV_NORMAL, 1, ks // 2, H, W
+    if kind == "s2":
+        return CONV_NORMAL, 2, 1, (H + 2 - ks) // 2 + 1, (W + 2 - ks) // 2 + 1
+    if kind == "s2asym":
+        return CONV_NORMAL, 2, 0, H // 2, W // 2
+    if kind == "up2":
+        return CONV_UP2, 1, 1, 2 * H, 2 * W
+    assert kind == "t2", kind
+    return CONV_T2, 1, 1, case["out_hw"][0], case["out_hw"][1]
+
+
+def conv_alpha(case):
+    """0.75; 1.0 for accumulate and for the Cout <= 3 cases (the direct small-Cout form needs alpha == 1, and the
+    strided-output case must miss that form through its row pitch alone)."""
+    return 1.0 if case["mode"] == "acc" or case["Cout"] <= 3 else 0.75
+
+
+def _nan_margined(t, margin, device):
+    """t as the interior of a flat buffer whose `margin` elements either side hold NaN (a tap that leaves the tensor
+    reads NaN, not a neighbouring allocation)."""
+    n = t.numel()
+    buf = torch.full((n + 2 * margin,), float("nan"), dtype=t.dtype)
+    buf[margin:margin + n] = t.reshape(-1)
+    return buf.to(device)[margin:margin + n].view(t.shape)
+
+
+def conv_inputs(case, dtype=None, device="cpu"):
+    """The operands of one conv case in the element type, drawn on the CPU from a seed derived from the geometry alone
+    (so "splitk" and "splitk-off" see the same numbers): x (and x2) NHWC inside NaN margins of at least (W + 2) * C
+    elements; w [Cout, ks, ks, C1 + C2] scaled by 1 / (ks sqrt(Ct)); by mode bias [Cout], rowbias [B, Cout], resid
+    [B, Ho, Wo, Cout], base (fp32, accumulate); a2 [M, K2] and w2 [Cout, K2] for the LoRA tail; alpha."""
+    et = _elem(dtype)
+    B, H, W, C1, C2, Cout, ks, K2, mode = (case[k] for k in ("B", "H", "W", "C1", "C2", "Cout", "ks", "K2", "mode"))
+    _, _, _, Ho, Wo = conv_geom(case)
+    Ct = C1 + C2
+    g = torch.Generator().manual_seed(_seed(len(case["kind"]), B, H, W, C1, C2, Cout, ks, K2, Ho, Wo, len(mode)))
+    dev = lambda t: t.to(et).to(device)
+    inp = dict(x=_nan_margined(torch.randn(B, H, W, C1, generator=g).to(et), (W + 2) * C1, device))
+    if C2:
+        inp["x2"] = _nan_margined(torch.randn(B, H, W, C2, generator=g).to(et), (W + 2) * C2, device)
+    inp["w"] = dev(torch.randn(Cout, ks, ks, Ct, generator=g) / (ks * Ct ** 0.5))
+    inp["alpha"] = conv_alpha(case)
+    if mode in ("full", "bias"):
+        inp["bias"] = dev(torch.randn(Cout, generator=g))
+    if mode == "full":
+        inp["rowbias"] = dev(torch.randn(B, Cout, generator=g))
+        inp["resid"] = dev(torch.randn(B, Ho, Wo, Cout, generator=g))
+    if mode == "acc":
+        inp["base"] = torch.randn(B, Ho, Wo, Cout, generator=g).to(device)
+    if K2:
+        inp["a2"] = dev(torch.randn(B * Ho * Wo, K2, generator=g))
+        inp["w2"] = dev(torch.randn(Cout, K2, generator=g) / 6)
+    return inp
+
+
+def _conv_torch(xc, wn, case):
+    """The case's convolution by torch's own operators: xc [B, Ct, H, W], wn [Cout, Ct, ks, ks] of one float type ->
+    [B, Cout, Ho, Wo].  No index formula of the kernels appears here."""
+    F = torch.nn.functional
+    kind = case["kind"]
+    if kind == "s1":
+        return F.conv2d(xc, wn, padding=case["ks"] // 2)
+    if kind == "s2":
+        return F.conv2d(xc, wn, stride=2, padding=1)
+    if kind == "s2asym":   # diffusers' Downsample2D of the VAE: pad (0, 1, 0, 1), then a stride-2 conv without padding
+        return F.conv2d(F.pad(xc, (0, 1, 0, 1)), wn, stride=2)
+    if kind == "up2":
+        return F.conv2d(F.interpolate(xc, scale_factor=2, mode="nearest"), wn, padding=1)
+    assert kind == "t2", kind
+    # the input gradient of y = conv2d(z, w_fwd, stride 2, pad 1) for dy = xc: w_fwd [Co, Ci, kh, kw] is the kernel's
+    # unflipped [Ci][kh][kw][Co] weight; linear in dy and w_fwd, so |dy|, |w| give the magnitude
+    Ho, Wo = case["out_hw"]
+    z = torch.zeros(xc.shape[0], wn.shape[0], Ho, Wo, dtype=xc.dtype, requires_grad=True)
+    y = F.conv2d(z, wn.permute(1, 0, 2, 3), stride=2, padding=1)
+    assert y.shape == xc.shape, (y.shape, xc.shape)
+    (gz,) = torch.autograd.grad(y, z, xc)
+    return gz
+
+
+def _conv_rows(t):
+    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])   # [B, Cout, Ho, Wo] -> [B * Ho * Wo, Cout]
+
+
+def conv_reference(inp, case):
+    """fp64 reference [M, Cout] and the element-wise bound of one conv case, on the CPU with torch's own operators
+    (_conv_torch: F.conv2d, F.pad, F.interpolate, torch.autograd.grad, torch.cat -- not the kernels' index formulae).
+    The bound is gemm_reference's with K = ks ks (C1 + C2):
+        u_out |ref| + (K + K2 + 8) 2^-23 (|alpha| (conv(|x|, |w|) + |a2| |w2|^T) + |bias| + |rowbias| + |resid or base|)
+    u_out = ELEM_ULP of the element type for a 16-bit output, 2^-23 for an fp32 one.  A 16-bit output with a residual
+    gets one more u_out |alpha acc + bias + rowbias|: the residual is added to the ROUNDED projection (gemm.hip "bf16
+    out: out = bf16(bf16(y) + resid)", the staged epilogue and gemm_splitk_reduce_kernel; gemm8p.hip EPI_NONE) -- a
+    documented rounding of the operation.  The magnitude term is the same torch operator on the absolute values."""
+    c64 = lambda t: t.detach().cpu().double()
+    et = inp["x"].dtype
+    x = c64(inp["x"])
+    if "x2" in inp:
+        x = torch.cat([x, c64(inp["x2"])], -1)
+    xc, wn = x.permute(0, 3, 1, 2), c64(inp["w"]).permute(0, 3, 1, 2)
+    y = _conv_rows(_conv_torch(xc, wn, case))
+    mag = _conv_rows(_conv_torch(xc.abs(), wn.abs(), case))
+    M, Cout = y.shape
+    K, K2 = case["ks"] * case["ks"] * (case["C1"] + case["C2"]), case["K2"]
+    if K2:
+        a2, w2 = c64(inp["a2"]), c64(inp["w2"])
+        y = y + a2 @ w2.t()
+        mag = mag + a2.abs() @ w2.abs().t()
+    proj, mag = inp["alpha"] * y, abs(inp["alpha"]) * mag
+    if "bias" in inp:
+        proj = proj + c64(inp["bias"])
+        mag = mag + c64(inp["bias"]).abs()
+    if "rowbias" in inp:
+        rb = c64(inp["rowbias"]).repeat_interleave(M // case["B"], 0)
+        proj, mag = proj + rb, mag + rb.abs()
+    ref = proj
+    for name in ("resid", "base"):
+        if name in inp:
+            t = c64(inp[name]).reshape(M, Cout)
+            ref, mag = proj + t, mag + t.abs()
+    f32_out = case["mode"] in ("f32", "acc")
+    u_out = U32 if f32_out else ELEM_ULP[et]
+    bound = u_out * ref.abs() + (K + K2 + 8) * U32 * mag
+    if "resid" in inp and not f32_out:
+        bound = bound + u_out * proj.abs()
+    return ref, bound
+
+
+CONV_FAULTS = ("wrap", "wrap-one-chunk", "replicate", "pad-top-left", "rowbias-tile", "t2-swap", "epilogue-per-split")
+
+
+def _conv_gather(x, case, fault=None, at=None):
+    """The implicit GEMM's A operand [M, ks ks Ct] (tap-major, channel-minor) of x [B, H, W, Ct], by the gather formulae
+    of gemm.hip's header (NORMAL iy = oy S + kh - P; UP2 iy = (oy + kh - P) >> 1 inside the 2x grid; T2 iy = (oy + P -
+    kh) / 2 where that is even, non-negative and below H), zero where a tap leaves the image.  fault: one of the planted
+    gather mistakes of CONV_FAULTS (a wrong bound wraps into the neighbouring row, never out of the image); at: the
+    output row oy of "wrap-one-chunk" (default Ho // 2)."""
+    mode, stride, pad, Ho, Wo = conv_geom(case)
+    B, H, W, Ct = x.shape
+    ks = case["ks"]
+    if fault == "pad-top-left":   # the asymmetric pad on the top and left instead of the bottom and right
+        pad = 1
+    oy = torch.arange(Ho).view(Ho, 1).expand(Ho, Wo)
+    ox = torch.arange(Wo).view(1, Wo).expand(Ho, Wo)
+    flat = x.reshape(B, H * W, Ct)
+    cols = []
+    for kh in range(ks):
+        for kw in range(ks):
+            if mode == CONV_NORMAL:
+                iy, ix = oy * stride + kh - pad, ox * stride + kw - pad
+                oky, okx = (iy >= 0) & (iy < H), (ix >= 0) & (ix < W)
+            elif mode == CONV_UP2:
+                uy, ux = oy + kh - pad, ox + kw - pad
+                oky, okx = (uy >= 0) & (uy < 2 * H), (ux >= 0) & (ux < 2 * W)
+                if fault == "replicate":   # the border pixel again instead of zero
+                    uy, ux, oky, okx = uy.clamp(0, 2 * H - 1), ux.clamp(0, 2 * W - 1), oky | True, okx | True
+                iy, ix = uy >> 1, ux >> 1
+            else:
+                ty, tx = oy + pad - kh, ox + pad - kw
+                iy, ix = ty >> 1, tx >> 1
+                hb, wb = (W, H) if fault == "t2-swap" else (H, W)   # H and W exchanged in the bound
+                oky, okx = (ty >= 0) & (ty % 2 == 0) & (iy < hb), (tx >= 0) & (tx % 2 == 0) & (ix < wb)
+            ok = oky & okx
+            wrapped = torch.zeros_like(ok)
+            if fault == "wrap":             # the horizontal bound forgotten: pixel iy W + ix of the neighbouring row
+                wrapped = oky & ~okx
+            elif fault == "wrap-one-chunk" and (kh, kw) == (1, 0):
+                # ... by one lane: one 16-byte chunk of the left tap of one left-edge pixel of the last image
+                wrapped[Ho // 2 if at is None else at, 0] = True
+            pix = iy * W + ix
+            inside = (pix >= 0) & (pix < H * W)
+            take = flat[:, pix.clamp(0, H * W - 1).reshape(-1), :]
+            g = take * (ok & inside).reshape(1, -1, 1).to(take.dtype)
+            if bool(wrapped.any()):
+                w_ = (wrapped & inside).reshape(1, -1, 1).to(take.dtype)
+                if fault == "wrap-one-chunk":
+                    w_ = w_.expand(B, -1, Ct).clone()
+                    w_[:B - 1] = 0          # the last image only
+                    w_[:, :, 8:] = 0        # channels 0 .. 7: one 16-byte chunk
+                g = g + take * w_
+            cols.append(g)
+    return torch.stack(cols, 2).reshape(B * Ho * Wo, ks * ks * Ct)
+
+
+def conv_restatement(inp, case, fault=None, at=None):
+    """The documented computation in fp32 torch: the gathered patch matrix times the weights with fp32 sums, the LoRA
+    tail, alpha, bias, the per-image row bias; a 16-bit output rounded to the element type, and once more after the
+    residual; fp32 accumulate onto base.  [M, Cout].  fault: one of CONV_FAULTS, planted for the self-test."""
+    assert fault is None or fault in CONV_FAULTS, fault
+    c32 = lambda t: t.detach().cpu().float()
+    et = inp["x"].dtype
+    x = c32(inp["x"])
+    if "x2" in inp:
+        x = torch.cat([x, c32(inp["x2"])], -1)
+    w = c32(inp["w"])
+    Cout = w.shape[0]
+    y = _conv_gather(x, case, fault, at) @ w.reshape(Cout, -1).t()
+    M = y.shape[0]
+    if "a2" in inp:
+        y = y + c32(inp["a2"]) @ c32(inp["w2"]).t()
+    y = inp["alpha"] * y
+    times = 2 if fault == "epilogue-per-split" else 1   # every one of the two K-splits adding the epilogue operands
+    if "bias" in inp:
+        y = y + times * c32(inp["bias"])
+    if "rowbias" in inp:
+        img = torch.arange(M) // (M // case["B"])
+        if fault == "rowbias-tile":   # the second 64-row tile takes its image from its first row
+            img[64:128] = img[64]
+        y = y + times * c32(inp["rowbias"])[img]
+    if case["mode"] == "acc":
+        return c32(inp["base"]).reshape(M, Cout) + y
+    if case["mode"] == "f32":
+        return y
+    y = y.to(et)
+    if "resid" in inp:
+        y = (y.float() + times * c32(inp["resid"]).reshape(M, Cout)).to(et)
+    return y
+
+
+def conv_plan_case(case_id):
+    """The case as tests/gemm_plan_cases.py describes a problem (the fields of PsoGemmPlanQuery that differ from its
+    defaults), with the operand alignments and row pitches run_conv_case hands over."""
+    c = CONV_CASES[case_id]
+    mode, stride, pad, Ho, Wo = conv_geom(c)
+    full, f32_out = c["mode"] == "full", c["mode"] in ("f32", "acc")
+    q = dict(entry="pso_conv2d_ws" if c["ws"] else "pso_conv2d", variant=c["variant"], conv_mode=mode, B=c["B"],
+             C1=c["C1"], C2=c["C2"], H=c["H"], W=c["W"], Ho=Ho, Wo=Wo, ks=c["ks"], stride=stride, pad=pad, N=c["Cout"],
+             K2=c["K2"], out_dtype=0 if f32_out else 1, accumulate=int(c["mode"] == "acc"),
+             alpha=conv_alpha(c),
+             bias_align=16 if c["mode"] in ("full", "bias") else 0, rowbias_align=16 if full else 0,
+             resid_align=16 if full else 0, out_align=16,
+             ldo=c["Cout"] if c["out"] == "flat" else guarded_pitch([c["Cout"]]))
+    return q
+
+
+def run_conv_case(cuda, case_id):
+    """One conv case end to end (tests/test_gpu_conv_guarded.py, and the fp16 library's in tests/test_gpu_f16.py): the
+    inputs inside NaN margins, the fp64 reference and derived bound from the CPU, the output a guarded column slice (or
+    guarded_flat where the form needs a dense one), the kernel name, the guard band, finiteness, zero violations."""
+    from pairwise_sample_optimization_amd import kernels as K
+    case = CONV_CASES[case_id]
+    mode, stride, pad, Ho, Wo = conv_geom(case)
+    B, Cout, K2 = case["B"], case["Cout"], case["K2"]
+    M, K1 = B * Ho * Wo, case["ks"] * case["ks"] * (case["C1"] + case["C2"])
+    inp = conv_inputs(case, K.ELEM, cuda)                                                          # 1.
+    ref, bound = conv_reference(inp, case)                                                         # 2.
+    f32_out = case["mode"] in ("f32", "acc")
+    odt = torch.float32 if f32_out else K.ELEM
+    if case["out"] == "flat":                                                                      # 3.
+        flat, check = guarded_flat(M * Cout, dtype=odt, device=cuda)
+        out = flat.view(B, Ho, Wo, Cout)
+        assert out.is_contiguous()
+    else:
+        (o2,), check = guarded(M, [Cout], dtype=odt, device=cuda)
+        out = o2.view(B, Ho, Wo, Cout)
+        assert not out.is_contiguous() and out.stride(2) == guarded_pitch([Cout]) > Cout
+    if case["mode"] == "acc":                                                                      # 4.
+        out.copy_(inp["base"])
+    kw = {k: inp[k] for k in ("x2", "bias", "rowbias", "resid", "a2", "w2") if k in inp}
+    K.gemm_set_variant(case["variant"])                                                            # 5.
+    try:
+        ws_bytes = K.lib().pso_conv2d_ws_bytes(B, Ho, Wo, Cout, K1, K2)
+        assert (ws_bytes > 0) == case["ws"], f"{case_id}: workspace {ws_bytes} bytes"              # 6.
+        got = K.conv2d(inp["x"], inp["w"], mode=mode, stride=stride, pad=pad, out_hw=(Ho, Wo), alpha=inp["alpha"],
+                       out=out, out_dtype=odt, accumulate=case["mode"] == "acc", **kw)             # 7.
+        name = K.lib().pso_last_kernel().decode()                                                  # 8.
+    finally:
+        K.gemm_set_variant(0)
+    torch.cuda.synchronize()                                                                       # 9.
+    assert got.data_ptr() == out.data_ptr()
+    assert name.startswith(case["kernel"]), f"{case_id}: ran {name}, wanted {case['kernel']}"      # 10.
+    check(f"conv {case_id}")                                                                       # 11.
+    got2 = out.reshape(M, Cout).cpu()
+    worst = ((got2.double() - ref).abs() / bound.clamp_min(_TINY)).max().item()
+    print(f"\n[conv {K.ELEM} {case_id}] {name}: worst |err| / bound {worst:.3f} over {got2.numel()} elements",
+          flush=True)                                                                              # 14. (before 12, 13)
+    assert torch.isfinite(got2.float()).all(), f"{case_id}: a non-finite output (a tap read the NaN margin?)"   # 12.
+    n, msg = violations(got2, ref, bound)                                                          # 13.
+    assert n == 0, f"{case_id} ({name}): {msg}"

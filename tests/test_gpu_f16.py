@@ -341,6 +341,15 @@ def test_layer_norm_localised(cuda):
     P.run_layer_norm_case(cuda, 7, 520)
 
 
+@pytest.mark.parametrize("case", ["s1-straddle", "s2asym-vae"])
+def test_conv_localised(cuda, case):
+    """Two conv cases of tests/test_gpu_conv_guarded.py on the fp16 library (two images per 64-row tile with ragged
+    M and N and the full epilogue; the VAE's asymmetric downsample): NaN-margined inputs, guarded output, the kernel
+    name, every element within the bound derived for fp16."""
+    import parity_util as P
+    P.run_conv_case(cuda, case)
+
+
 def test_geglu_elementwise_fwd_bwd(cuda):
     from pairwise_sample_optimization_amd import kernels as Kk
     g = _gen(14)

@@ -729,20 +729,34 @@ def test_fullgrad_helpers(cuda):
     dg2, db2 = torch.zeros(C, device=cuda), torch.zeros(C, device=cuda)
     K_.layer_norm_dparam(xl, dy, st, dg2, db2)
     assert torch.equal(dg, dg2) and torch.equal(db, db2)
-    for mode, stride, C1, C2 in [(K_.CONV_NORMAL, 1, 64, 0), (K_.CONV_NORMAL, 2, 32, 0), (K_.CONV_UP2, 1, 32, 0),
-                                 (K_.CONV_NORMAL, 1, 64, 32)]:
-        B, H, W = 2, 9, 7
+    # (mode, stride, C1, C2, H, W, spare): 9 x 7 odd sizes; 8 x 6 even with stride 2 (only the top / left pad is
+    # touched); UP2 over two sources; spare > 0: the patch matrix is the leading columns of a wider buffer (ldo >
+    # 9 * Ct) whose spare columns must keep their previous contents
+    for mode, stride, C1, C2, H, W, spare in [(K_.CONV_NORMAL, 1, 64, 0, 9, 7, 0), (K_.CONV_NORMAL, 2, 32, 0, 9, 7, 0),
+                                              (K_.CONV_UP2, 1, 32, 0, 9, 7, 0), (K_.CONV_NORMAL, 1, 64, 32, 9, 7, 0),
+                                              (K_.CONV_NORMAL, 2, 32, 0, 8, 6, 0), (K_.CONV_UP2, 1, 32, 16, 5, 3, 0),
+                                              (K_.CONV_NORMAL, 1, 32, 16, 9, 7, 24)]:
+        B = 2
         x1 = torch.randn(B, H, W, C1, device=cuda, generator=g).bfloat16()
         x2 = torch.randn(B, H, W, C2, device=cuda, generator=g).bfloat16() if C2 else None
-        cols = K_.im2col_conv(x1, x2, mode=mode, stride=stride)
+        Ct = C1 + C2
+        if spare:  # the entry itself: kernels.im2col_conv always hands it a dense matrix
+            Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+            wide = torch.randn(B * Ho * Wo, 9 * Ct + spare, device=cuda, generator=g).bfloat16()
+            kept = wide[:, 9 * Ct:].clone()
+            _lib.check(K_.lib().pso_im2col_conv(mode, B, _lib.ptr(x1), C1, _lib.ptr(x2), C2, H, W, Ho, Wo, stride, 1,
+                                                _lib.ptr(wide), wide.stride(0), _lib.stream_ptr()), "pso_im2col_conv")
+            cols = wide[:, :9 * Ct]
+            assert torch.equal(wide[:, 9 * Ct:], kept), "the spare columns were written"
+        else:
+            cols = K_.im2col_conv(x1, x2, mode=mode, stride=stride)
         xc = torch.cat([x1, x2], -1) if C2 else x1
         xn = xc.permute(0, 3, 1, 2).float()
         if mode == K_.CONV_UP2:
             xn = F.interpolate(xn, scale_factor=2.0, mode="nearest")
         u = F.unfold(xn, 3, padding=1, stride=stride)                 # [B, C*9, L] with (c, ky, kx) order
-        Ct = C1 + C2
         u = u.view(B, Ct, 9, -1).permute(0, 3, 2, 1).reshape(-1, 9 * Ct)  # -> (pixel, tap, c)
-        assert cols.shape == u.shape and torch.equal(cols.float(), u), (mode, stride, C1, C2)
+        assert cols.shape == u.shape and torch.equal(cols.float(), u), (mode, stride, C1, C2, H, W, spare)
 
 
 def test_tn_rank_batch_equals_individual_products(cuda):

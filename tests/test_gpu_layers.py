@@ -300,6 +300,29 @@ def test_transpose_im2col_sumpool_weight_t(cuda):
     assert torch.equal(K.conv_weight_t(wt, False), wt.permute(3, 1, 2, 0).contiguous())
 
 
+def test_sumpool2_dadd_elementwise(cuda):
+    """sumpool2 with dadd (the upsampler's input gradient plus the gradient already there) on a non-square 2 x 6 x 10 x
+    64 input, element-wise against the fp64 sum: |err| <= u_out |ref| + 8 * 2^-23 (sum of the four |u| + |dadd|) -- one
+    rounding to the element type and five fp32 additions in any order."""
+    from pairwise_sample_optimization_amd import kernels as K
+    g = torch.Generator().manual_seed(62)
+    u = torch.randn(2, 6, 10, 64, generator=g).to(K.ELEM).to(cuda)
+    dadd = torch.randn(2, 3, 5, 64, generator=g).to(K.ELEM).to(cuda)
+    got = K.sumpool2(u, dadd=dadd)
+    assert got.shape == (2, 3, 5, 64) and got.dtype == K.ELEM
+    ud, dd = u.double().cpu(), dadd.double().cpu()
+    blocks = ud.reshape(2, 3, 2, 5, 2, 64)           # [b, y, dy, x, dx, c]
+    ref = blocks.sum((2, 4)) + dd
+    bound = P.ELEM_ULP[K.ELEM] * ref.abs() + 8 * P.U32 * (blocks.abs().sum((2, 4)) + dd.abs())
+    n, msg = P.violations(got.cpu().reshape(-1, 64), ref.reshape(-1, 64), bound.reshape(-1, 64))
+    assert n == 0, msg
+    # without dadd the same input gives the plain block sum
+    n, msg = P.violations(K.sumpool2(u).cpu().reshape(-1, 64), blocks.sum((2, 4)).reshape(-1, 64),
+                          (P.ELEM_ULP[K.ELEM] * blocks.sum((2, 4)).abs() + 8 * P.U32 * blocks.abs().sum((2, 4)))
+                          .reshape(-1, 64))
+    assert n == 0, msg
+
+
 @pytest.mark.parametrize("shape", [(640, 3, 3, 320), (1280, 3, 3, 2560), (4, 3, 3, 320), (320, 3, 3, 4), (100, 1, 1, 72),
                                    (70, 3, 3, 12)])
 def test_conv_weight_t_shapes(cuda, shape):

@@ -27,7 +27,8 @@ def test_knob_forms_in_tools_build(cuda, capsys):
            os.path.join(ROOT, "tests", "test_gpu_kernels.py"), os.path.join(ROOT, "tests", "test_gpu_layers.py"),
            os.path.join(ROOT, "tests", "test_gpu_determinism.py"),
            os.path.join(ROOT, "tests", "test_gpu_attention_layout.py"),
-           os.path.join(ROOT, "tests", "test_gpu_gemm_guarded.py")]
+           os.path.join(ROOT, "tests", "test_gpu_gemm_guarded.py"),
+           os.path.join(ROOT, "tests", "test_gpu_conv_guarded.py")]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=1400)
     tail = (r.stdout[-4000:] + r.stderr[-2000:])
     with capsys.disabled():  # the child's summary line belongs in the suite log

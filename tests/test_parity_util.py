@@ -1,7 +1,8 @@
 """CPU self-test of tests/parity_util.py: the helper that the localised-error GPU parity tests stand on is itself
 checked here, with no kernel involved -- the rounding model against fp64 on every attention shape the GPU tests use,
-the guard-band detector, the reason the per-row metric exists, and the derived GEGLU / GEMM element-wise bounds against
-a torch restatement of the documented computation (zero violations)."""
+the guard-band detector, the reason the per-row metric exists, and the derived GEGLU / GEMM / convolution element-wise
+bounds against a torch restatement of the documented computation (zero violations), with planted faults that must land
+outside them; the conv cases' dispatch is asked of the plan query, which launches nothing."""
 import functools
 import math
 
@@ -334,3 +335,166 @@ def test_norm_detector_neighbours_coefficients_land_outside_the_chunk_bound(dtyp
     one[1, 5] = coef[1, 6]
     e = P.rowwise_rel(P.group_norm_model(*args, coef=one)[2], ref["dx"], 8)
     assert e > bound and e.index[0] == 1 and e.index[2] in (50 // 8, 59 // 8, 6, 7), e
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# convolutions
+# ----------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _conv_case(case_id, dtype):
+    """(inputs, fp64 reference, bound) of one conv case, computed once and shared (read-only) by the tests below."""
+    case = P.CONV_CASES[case_id]
+    inp = P.conv_inputs(case, dtype, "cpu")
+    return (inp,) + P.conv_reference(inp, case)
+
+
+def test_conv_case_table_is_the_issued_one():
+    """The ids, split between the product dispatch and the knob-pinned forms, and the facts the cases are about: two
+    images in one 64-row tile with a ragged last tile, non-square images everywhere but the 8-phase one-tile cases,
+    the asymmetric downsample's last tap past the bottom and right edge."""
+    assert len(P.CONV_DEFAULT_IDS) == 19 and len(P.CONV_KNOB_IDS) == 10
+    for cid, c in P.CONV_CASES.items():
+        _, _, _, Ho, Wo = P.conv_geom(c)
+        assert c["B"] * Ho * Wo <= (1024 if c["Cout"] <= 3 else 768), cid   # small on purpose
+        assert c["H"] != c["W"] or cid in ("8p-one-tile", "8p-three-images"), cid
+    c = P.CONV_CASES["s1-straddle"]
+    assert (c["H"] * c["W"], c["B"] * c["H"] * c["W"]) == (63, 189) and c["Cout"] % 64
+    c = P.CONV_CASES["s2asym-vae"]
+    assert P.conv_geom(c)[1:] == (2, 0, 5, 3) and 2 * (5 - 1) + 2 == c["H"] and 2 * (3 - 1) + 2 == c["W"]
+    assert P.conv_geom(P.CONV_CASES["s2-odd"])[3:] == (5, 4) and P.conv_geom(P.CONV_CASES["s2-even"])[3:] == (4, 3)
+    inp = P.conv_inputs(P.CONV_CASES["s1-concat"], torch.bfloat16, "cpu")
+    for n in ("x", "x2"):   # the images end where the NaN begins, at least (W + 2) * C elements of it either side
+        t = inp[n]
+        base, off, C = t._base, t.storage_offset(), t.shape[3]
+        assert off >= (t.shape[2] + 2) * C and base.numel() - off - t.numel() >= (t.shape[2] + 2) * C
+        assert torch.isnan(base[:off]).all() and torch.isnan(base[off + t.numel():]).all() and torch.isfinite(t).all()
+        assert off % 8 == 0 and t.is_contiguous()
+
+
+@_DTYPES
+def test_conv_bound_holds_for_the_restatement(dtype):
+    """conv_restatement (the documented gather and roundings, in fp32 torch) against conv_reference (fp64, torch's own
+    conv operators) on every case id: zero violations of the derived bound.  It also ties the two descriptions of each
+    gather mode to one another.  The worst ratios are recorded beside P.CONV_CASES."""
+    worst = {}
+    for cid, case in P.CONV_CASES.items():
+        inp, ref, bound = _conv_case(cid, dtype)
+        got = P.conv_restatement(inp, case)
+        assert got.dtype == (torch.float32 if case["mode"] in ("f32", "acc") else dtype)
+        n, msg = P.violations(got, ref, bound)
+        worst[cid] = ((got.double() - ref).abs() / bound).max().item()
+        print(f"conv {cid} {dtype}: worst |err| / bound {worst[cid]:.3f} over {got.numel()} elements")
+        assert n == 0, (cid, msg)
+        assert P.violations(torch.roll(got, 1, 0), ref, bound)[0] > got.numel() // 2, cid   # the next pixel's row
+    print(f"conv {dtype}: worst over all ids {max(worst.values()):.3f} ({max(worst, key=worst.get)})")
+    assert 0.3 < max(worst.values()) <= 1.0   # a 16-bit rounding uses a good part of its unit roundoff
+
+
+_CONV_DETECTORS = [("wrap", "s1-straddle"), ("replicate", "up2"), ("pad-top-left", "s2asym-vae"),
+                   ("rowbias-tile", "s1-straddle"), ("t2-swap", "t2-even"), ("epilogue-per-split", "splitk")]
+
+
+@_DTYPES
+@pytest.mark.parametrize("fault,case_id", _CONV_DETECTORS)
+def test_conv_detectors_planted_faults_land_outside_the_bound(fault, case_id, dtype):
+    """Each planted fault of the restatement gives at least one violation; the whole-tensor ratio is printed beside."""
+    case = P.CONV_CASES[case_id]
+    inp, ref, bound = _conv_case(case_id, dtype)
+    bad = P.conv_restatement(inp, case, fault)
+    n, msg = P.violations(bad, ref, bound)
+    print(f"conv detector {fault} on {case_id} {dtype}: {n} of {bad.numel()} elements outside the bound, whole-tensor "
+          f"ratio {P.frob_rel(bad, ref):.3e}")
+    assert n >= 1, (fault, case_id)
+    if fault == "rowbias-tile":   # rows 126, 127: the two pixels of image 2 inside the tile that starts in image 1
+        err = (bad.double() - ref).abs() > bound
+        assert set(err.any(1).nonzero().reshape(-1).tolist()) == {126, 127}
+
+
+@_DTYPES
+def test_conv_wrapped_tap_is_invisible_to_the_whole_tensor_ratio(dtype):
+    """The first detector against the metric of the older conv tests.  With the horizontal bound missing at every
+    left / right edge pixel of this 9 x 7 image the whole-tensor ratio is large too (2 of 7 pixel columns are wrong);
+    what that ratio cannot see is the mistake one lane makes: one 16-byte chunk of the left tap of ONE edge pixel
+    taken from the neighbouring row.  Planted at each left-edge pixel of the last image in turn: the element-wise bound
+    finds every one of them and names the pixel; the 4e-3 ratio the older tests assert lets some of them pass (measured:
+    3 of 8 in bf16, 5 of 8 in fp16, the others reach at most 6e-3 -- and on the older tests' own, larger shapes one
+    pixel is a far smaller share of the tensor than 1 / 189 here)."""
+    case = P.CONV_CASES["s1-straddle"]
+    inp, ref, bound = _conv_case("s1-straddle", dtype)
+    assert P.frob_rel(P.conv_restatement(inp, case), ref) < 4e-3
+    assert P.frob_rel(P.conv_restatement(inp, case, "wrap"), ref) > 4e-3
+    passed = []
+    for oy in range(1, case["H"]):   # row 0 has no neighbouring row above inside the image
+        bad = P.conv_restatement(inp, case, "wrap-one-chunk", at=oy)
+        n, _ = P.violations(bad, ref, bound)
+        fr = P.frob_rel(bad, ref)
+        rows = ((bad.double() - ref).abs() > bound).any(1).nonzero().reshape(-1).tolist()
+        print(f"one wrapped chunk at row {oy} {dtype}: {n} elements outside the bound, whole-tensor ratio {fr:.3e}")
+        assert n >= 1 and rows == [2 * 63 + oy * 7], (oy, n, rows)
+        passed.append(fr < 4e-3)
+    assert any(passed), passed
+
+
+def test_guarded_flat_detects_only_outside_writes():
+    for dtype in (torch.bfloat16, torch.float16, torch.float32):
+        view, check = P.guarded_flat(1000, dtype=dtype, device="cpu", pad=64)
+        assert view.shape == (1000,) and view.is_contiguous() and view.data_ptr() % 16 == 0
+        assert torch.isnan(view).all()
+        check()
+        view.copy_(torch.randn(1000))   # a write inside the view is the kernel's business
+        view[999] = float("nan")
+        check()
+        base = view._base
+        for i in (0, 63, 64 + 1000, 64 + 1000 + 63):   # before the view, and after it
+            base[i] = 0.0
+            with pytest.raises(AssertionError, match=rf"first at {i} of"):
+                check()
+            base[i] = float("nan")          # a canonical NaN is not the fill either
+            with pytest.raises(AssertionError, match=rf"first at {i} of"):
+                check()
+            base.view(torch.int32 if dtype == torch.float32 else torch.int16)[i] = P.FILL_BITS[view.element_size()]
+            check()
+
+
+_CONV_PLAN_PROBE = """
+import ctypes, json, sys
+sys.path.insert(0, "tests")
+import gemm_plan_cases as C
+import parity_util as P
+from pairwise_sample_optimization_amd import _lib
+l = _lib.lib()
+got = {}
+for cid in P.CONV_CASES:
+    case = P.conv_plan_case(cid)
+    q, info = _lib.PsoGemmPlanQuery(**C.full(case)), _lib.PsoGemmPlanInfo()
+    rc = l.pso_gemm_plan_query(C.PLAN_CONV, ctypes.byref(q), ctypes.byref(info))
+    got[cid] = C.plan_of_info(C.PLAN_CONV, info) if rc == 0 else ["error", rc, l.pso_last_error().decode()]
+json.dump(got, sys.stdout)
+"""
+
+
+def test_conv_cases_plan_their_named_forms():
+    """Every conv case id, with the operand alignments and row pitches run_conv_case hands over, plans the form its
+    kernel name says (csrc/gemm_plan.h through pso_gemm_plan_query, which launches nothing; a PSO_LIB=knobs child as in
+    tests/test_gemm_plan_cpu.py): the tile, the conv mode (1 NORMAL, 2 UP2, 3 T2), the workspace K-splits, the 8-phase
+    conv form, the direct small-Cout kernel -- and the strided-output Cout = 3 case NOT the direct kernel."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import gemm_plan_cases as C
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k != "PSO_LIB_PATH"}
+    env["PSO_LIB"] = "knobs"
+    r = subprocess.run([sys.executable, "-c", _CONV_PLAN_PROBE], env=env, cwd=root, capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    got = json.loads(r.stdout)
+    assert set(got) == set(P.CONV_CASES)
+    wrong = {cid: (got[cid], C.plan_of_kernel(c["kernel"], c["ws_ks"])) for cid, c in P.CONV_CASES.items()
+             if got[cid] != C.plan_of_kernel(c["kernel"], c["ws_ks"])}
+    assert not wrong, f"(planned, named): {wrong}"
+    modes = {cid: got[cid][7] for cid, c in P.CONV_CASES.items() if got[cid][0] == "tile"}
+    assert modes["up2"] == P.CONV_UP2 and modes["t2-odd"] == modes["t2-even"] == P.CONV_T2
+    assert modes["small-strided-out"] == P.CONV_NORMAL and got["small-c3"][0] == "small_conv"
+    assert got["splitk"][9] == got["splitk-concat"][9] == 2 and got["splitk-off"][9] == 0
