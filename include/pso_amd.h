@@ -717,6 +717,17 @@ int pso_patchify(int B, int C, int S, int P, int kpad, const float* x, void* out
 size_t pso_clip_preprocess_ws_bytes(int B, int H, int W, int size);
 int pso_clip_preprocess(int B, int H, int W, const void* img, int img_dtype, int size, int patch, int kpad,
                         const float* mean, const float* stdv, void* out, void* ws, size_t ws_bytes, void* stream);
+/* pso_clip_preprocess keyed by an image kind of its own instead of a dtype code, so that uint8 images and images of
+ * the library's 16-bit element type stay apart in the f16 library as well (there PSO_U8 == PSO_F16).  PSO_IMG_ELEM
+ * quantises as torch executes ((x + 1.0) * 127.5).clamp(0, 255).to(torch.uint8) on a tensor of the element type: the
+ * sum and the product are each rounded to it (bf16, or IEEE fp16 round-to-nearest-even), then clamp, then truncate.
+ * Same workspace (pso_clip_preprocess_ws_bytes), argument checks, resize, crop, normalisation and output layout as
+ * pso_clip_preprocess, and the same bits for every input that entry accepts; any other img_kind is PSO_ERR_ARG. */
+#define PSO_IMG_F32 0
+#define PSO_IMG_ELEM 1 /* the library's 16-bit element type: bf16, or fp16 in the f16 library */
+#define PSO_IMG_U8 2
+int pso_clip_preprocess_img(int B, int H, int W, const void* img, int img_kind, int size, int patch, int kpad,
+                            const float* mean, const float* stdv, void* out, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,8 @@ PSO_F16 = 2
 # the library's 16-bit element type (checked against pso_elem_dtype() at load)
 ELEM_DTYPE = torch.float16 if F16 else torch.bfloat16
 ELEM_CODE = PSO_F16 if F16 else PSO_BF16
+# image kinds of pso_clip_preprocess_img (include/pso_amd.h PSO_IMG_*): not dtype codes
+IMG_F32, IMG_ELEM, IMG_U8 = 0, 1, 2
 MODE_TURBO = 0
 MODE_DMD = 1
 MODE_DMD_F16 = 2   # DMD2 latent-dtype replay modes (include/pso_amd.h PSO_MODE_DMD_F16 / _BF16)
@@ -92,6 +94,7 @@ SIGNATURES = {
     "pso_patchify": (ci, [ci, ci, ci, ci, ci, vp, vp, vp]),
     "pso_clip_preprocess_ws_bytes": (csz, [ci, ci, ci, ci]),
     "pso_clip_preprocess": (ci, [ci, ci, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, csz, vp]),
+    "pso_clip_preprocess_img": (ci, [ci, ci, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, csz, vp]),
     "pso_gemm_tn": (ci, [ci, ci, ci, vp, cl, vp, cl, cf, vp, cl, vp]),
     "pso_gemm_tn_grouped": (ci, [ci, ci, ci, vp, cl, vp, cl, cf, vp, cl, ci, vp]),
     "pso_gemm_tn_geglu": (ci, [ci, ci, ci, vp, cl, vp, cl, cf, vp, cl, vp]),
@@ -244,10 +247,19 @@ def require_knobs(what):
 
 def require_bf16(what):
     """Paths that were verified against their oracles in bf16 only raise under the f16 library instead of running
-    unverified: the fp8 forward, full-UNet training, clip.py."""
+    unverified: the fp8 forward, full-UNet training (clip.py has an opt-in: require_bf16_or_opt_in)."""
     if F16:
         raise PsoLibError(f"{what} is not supported by the f16 library (PSO_LIB=f16, libpso_amd_f16.so): unset "
                           "PSO_LIB and run it on the bf16 library")
+
+
+def require_bf16_or_opt_in(what, allow_f16):
+    """The CLIP towers and their image path (clip.py, kernels.clip_preprocess): refused under the f16 library unless
+    the caller opts in with allow_f16=True -- the default refusal is part of that library's contract.  Under a bf16
+    library the keyword changes nothing."""
+    if F16 and not allow_f16:
+        raise PsoLibError(f"{what} is not supported by the f16 library (PSO_LIB=f16, libpso_amd_f16.so) by default: "
+                          "pass allow_f16=True to run it in fp16, or unset PSO_LIB and run it on the bf16 library")
 
 
 def lib():

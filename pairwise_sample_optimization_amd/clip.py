@@ -19,6 +19,12 @@ visual_projection (no bias).
 Layout: token rows [B * S][C] bf16; q/k/v fused into one GEMM per layer; attention by `pso_attention_small`
 (short sequences, head dim 64 / 80); LayerNorm by `pso_layer_norm_fwd`; activations in place.  Forward only (frozen
 towers: the reference runs them under torch.no_grad()).
+
+Element type: "bf16" above means the loaded library's 16-bit element type (`_lib.ELEM_DTYPE`).  Under the f16 library
+(PSO_LIB=f16) the constructors refuse by default and build with `allow_f16=True`: parameters, token rows and patch rows
+are then fp16, softmax state and GEMM accumulators stay fp32, `logit_scale` stays fp32.  Under a bf16 library the
+keyword is accepted and ignored.  Activation headroom against fp16's 65504 with trained weights is for the user to
+check (tools/clip_f16_range.py).
 """
 import math
 from dataclasses import dataclass, fields
@@ -31,7 +37,7 @@ from . import _lib
 from . import kernels as K
 from .unet import Linear, Norm, _param
 
-BF16 = torch.bfloat16
+ELEM = _lib.ELEM_DTYPE  # the loaded library's 16-bit element type: bf16, or fp16 under PSO_LIB=f16 (allow_f16=True)
 
 
 @dataclass
@@ -177,9 +183,9 @@ class _TextEmbeddings(nn.Module):
 
 
 class CLIPTextTransformer(nn.Module):
-    def __init__(self, cfg: CLIPTextConfig):
+    def __init__(self, cfg: CLIPTextConfig, allow_f16=False):
         super().__init__()
-        _lib.require_bf16("clip.py (CLIPTextTransformer: PickScore and the text encoders)")
+        _lib.require_bf16_or_opt_in("clip.py (CLIPTextTransformer: PickScore and the text encoders)", allow_f16)
         self.cfg = cfg
         self.embeddings = _TextEmbeddings(cfg)
         self.encoder = CLIPEncoder(cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads,
@@ -231,22 +237,23 @@ class _TextModelBase(nn.Module):
     config_class = CLIPTextConfig
 
     @classmethod
-    def from_config(cls, config=None, **kw):
+    def from_config(cls, config=None, allow_f16=False, **kw):
         if isinstance(config, dict):
             config = _from_dict(CLIPTextConfig, dict(config, **kw))
-        return cls(config or CLIPTextConfig())
+        return cls(config or CLIPTextConfig(), allow_f16=allow_f16)
 
     @classmethod
-    def from_pretrained(cls, path, subfolder=None, torch_dtype=None, variant=None, revision=None, **kw):
+    def from_pretrained(cls, path, subfolder=None, torch_dtype=None, variant=None, revision=None, allow_f16=False,
+                        **kw):
         """`CLIPTextModel[WithProjection].from_pretrained(path, subfolder="text_encoder[_2]")` (T:252-266) from a
         local transformers directory (config.json + model.safetensors / pytorch_model.bin)."""
         from . import hf_io
-        m = cls.from_config(hf_io.load_config(path, subfolder))
+        m = cls.from_config(hf_io.load_config(path, subfolder), allow_f16=allow_f16)
         m.load_state_dict(hf_io.load_weights(path, subfolder, variant))
         return m
 
     def load_state_dict(self, sd, strict=True):
-        sd = {k: v.to(BF16) for k, v in sd.items() if not k.endswith("position_ids")}
+        sd = {k: v.to(ELEM) for k, v in sd.items() if not k.endswith("position_ids")}
         res = super().load_state_dict(sd, strict=strict)
         self._prepared = False
         return res
@@ -265,10 +272,10 @@ class CLIPTextModel(_TextModelBase):
     """transformers CLIPTextModel (keys `text_model.*`).  Call: `enc(ids, output_hidden_states=True)` -> object with
     [0] / .last_hidden_state, [1] / .pooler_output and .hidden_states (a lazy list: only [-2] and [-1] are formed)."""
 
-    def __init__(self, config: CLIPTextConfig = None):
+    def __init__(self, config: CLIPTextConfig = None, allow_f16=False):
         super().__init__()
         self.config = config or CLIPTextConfig()
-        self.text_model = CLIPTextTransformer(self.config)
+        self.text_model = CLIPTextTransformer(self.config, allow_f16=allow_f16)
         self._prepared = False
 
     def init_weights(self, seed=0):
@@ -295,10 +302,10 @@ class CLIPTextModelWithProjection(_TextModelBase):
     """transformers CLIPTextModelWithProjection (keys `text_model.*`, `text_projection.weight`): output [0] /
     .text_embeds = text_projection(pooled), .last_hidden_state, .hidden_states (lazy: [-2] formed)."""
 
-    def __init__(self, config: CLIPTextConfig = None):
+    def __init__(self, config: CLIPTextConfig = None, allow_f16=False):
         super().__init__()
         self.config = config or CLIPTextConfig.sdxl_bigg()
-        self.text_model = CLIPTextTransformer(self.config)
+        self.text_model = CLIPTextTransformer(self.config, allow_f16=allow_f16)
         self.text_projection = Linear(self.config.hidden_size, self.config.projection_dim, bias=False)
         self._prepared = False
 
@@ -367,9 +374,9 @@ class _ConvNoBias(nn.Module):
 
 
 class CLIPVisionTransformer(nn.Module):
-    def __init__(self, cfg: CLIPVisionConfig):
+    def __init__(self, cfg: CLIPVisionConfig, allow_f16=False):
         super().__init__()
-        _lib.require_bf16("clip.py (CLIPVisionTransformer: PickScore and the text encoders)")
+        _lib.require_bf16_or_opt_in("clip.py (CLIPVisionTransformer: PickScore and the text encoders)", allow_f16)
         self.cfg = cfg
         self.embeddings = _VisionEmbeddings(cfg)
         self.pre_layrnorm = Norm(cfg.hidden_size)
@@ -395,7 +402,7 @@ class CLIPVisionTransformer(nn.Module):
     def prepare(self):
         c = self.cfg
         w = self.embeddings.patch_embedding.weight.data.reshape(c.hidden_size, -1)  # (channel, ky, kx) order
-        self.w_patch = torch.zeros(c.hidden_size, self.kpad, device=w.device, dtype=BF16)
+        self.w_patch = torch.zeros(c.hidden_size, self.kpad, device=w.device, dtype=ELEM)
         self.w_patch[:, :w.shape[1]] = w
         for l in self.encoder.layers:
             l.prepare()
@@ -426,39 +433,40 @@ class CLIPModel(nn.Module):
     image path `image_features_from_images` (pso_clip_preprocess -> patch GEMM -> tower -> projection)."""
 
     def __init__(self, text_config: CLIPTextConfig = None, vision_config: CLIPVisionConfig = None,
-                 projection_dim=None):
+                 projection_dim=None, allow_f16=False):
         super().__init__()
+        self.allow_f16 = bool(allow_f16)  # opt-in to the f16 library (ignored under bf16); handed on to clip_preprocess
         self.text_config = text_config or CLIPTextConfig.pickscore_h()
         self.vision_config = vision_config or CLIPVisionConfig()
         pd = projection_dim or self.vision_config.projection_dim
         self.config = SimpleNamespace(text_config=self.text_config, vision_config=self.vision_config,
                                       projection_dim=pd)
-        self.text_model = CLIPTextTransformer(self.text_config)
-        self.vision_model = CLIPVisionTransformer(self.vision_config)
+        self.text_model = CLIPTextTransformer(self.text_config, allow_f16=allow_f16)
+        self.vision_model = CLIPVisionTransformer(self.vision_config, allow_f16=allow_f16)
         self.visual_projection = Linear(self.vision_config.hidden_size, pd, bias=False)
         self.text_projection = Linear(self.text_config.hidden_size, pd, bias=False)
         self.logit_scale = nn.Parameter(torch.tensor(math.log(1 / 0.07)), requires_grad=False)
         self._prepared = False
 
     @classmethod
-    def from_config(cls, config):
+    def from_config(cls, config, allow_f16=False):
         if isinstance(config, dict):
             pd = config.get("projection_dim")
             tc = _from_dict(CLIPTextConfig, dict(config.get("text_config", {}), projection_dim=pd or 512))
             vc = _from_dict(CLIPVisionConfig, dict(config.get("vision_config", {}), projection_dim=pd or 512))
-            return cls(tc, vc, pd)
-        return cls()
+            return cls(tc, vc, pd, allow_f16=allow_f16)
+        return cls(allow_f16=allow_f16)
 
     @classmethod
-    def from_pretrained(cls, path, subfolder=None, **kw):
+    def from_pretrained(cls, path, subfolder=None, allow_f16=False, **kw):
         """`AutoModel.from_pretrained("yuvalkirstain/PickScore_v1")` (pickscore_utils.py:20-23) from a local dir."""
         from . import hf_io
-        m = cls.from_config(hf_io.load_config(path, subfolder))
+        m = cls.from_config(hf_io.load_config(path, subfolder), allow_f16=allow_f16)
         m.load_state_dict(hf_io.load_weights(path, subfolder, None))
         return m
 
     def load_state_dict(self, sd, strict=True):
-        sd = {k: (v.float() if k == "logit_scale" else v.to(BF16)) for k, v in sd.items()
+        sd = {k: (v.float() if k == "logit_scale" else v.to(ELEM)) for k, v in sd.items()
               if not k.endswith("position_ids")}
         res = super().load_state_dict(sd, strict=strict)
         self._prepared = False
@@ -508,5 +516,6 @@ class CLIPModel(nn.Module):
     def image_features_from_images(self, img_nhwc, mean=CLIP_MEAN, std=CLIP_STD):
         """Decoded images NHWC bf16 in [-1, 1] -> image features, the whole T:632-640 + processor path on the GPU."""
         vc = self.vision_config
-        patches = K.clip_preprocess(img_nhwc, vc.image_size, vc.patch_size, self.vision_model.kpad, mean, std)
+        patches = K.clip_preprocess(img_nhwc, vc.image_size, vc.patch_size, self.vision_model.kpad, mean, std,
+                                    allow_f16=self.allow_f16)
         return self.get_image_features(patches=patches)

@@ -12,7 +12,8 @@
 //   * row_mean_kernel    - per-image mean (light_reward)
 //   * clip_preprocess    - [-1,1] image -> uint8 (the trainer's quantisation, in the image dtype) -> PIL bicubic
 //                          (antialiased, 8-bit fixed point, horizontal then vertical pass) -> crop -> /255 ->
-//                          (x - mean) / std -> 14x14 patch rows for the patch-embedding GEMM
+//                          (x - mean) / std -> 14x14 patch rows for the patch-embedding GEMM; the _img entry takes
+//                          an image kind instead of a dtype code (fp16 images in the f16 library)
 #include <math.h>
 #include <map>
 #include <mutex>
@@ -241,6 +242,40 @@ __global__ void resample_h_kernel(int H, int W, int OW, int y0, int rows, const 
   }
 }
 
+// resample_h_kernel keyed by image kind (PSO_IMG_*) instead of a dtype code, so a uint8 image and an image of the
+// library's 16-bit element type stay apart in the f16 library too (PSO_U8 == PSO_F16 == 2).  PSO_IMG_ELEM quantises
+// as torch does on a tensor of that type: the sum and the product are each rounded to it (bf16, or IEEE fp16
+// round-to-nearest-even: an overflowing product is +inf and clamps to 255), then clamp, then truncate.
+__global__ void resample_h_img_kernel(int H, int W, int OW, const void* __restrict__ img, int img_kind,
+                                      const int* __restrict__ bounds, const int* __restrict__ coef, int ksize,
+                                      uint8_t* __restrict__ tmp) {
+  const int b = blockIdx.y;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (long)H * OW * 3; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % 3);
+    const int ox = (int)((i / 3) % OW);
+    const int y = (int)(i / (3L * OW));
+    const int xmin = bounds[2 * ox], xn = bounds[2 * ox + 1];
+    const long base = (((long)b * H + y) * W) * 3 + c;
+    long ss = 1L << (PIL_PREC - 1);
+    for (int x = 0; x < xn; ++x) {
+      const long e = base + (long)(xmin + x) * 3;
+      int u;
+      if (img_kind == PSO_IMG_U8) {
+        u = reinterpret_cast<const uint8_t*>(img)[e];
+      } else {
+        float t;
+        if (img_kind == PSO_IMG_ELEM)
+          t = bf_round(bf_round(bf2f(reinterpret_cast<const bf16_t*>(img)[e]) + 1.0f) * 127.5f);
+        else
+          t = (reinterpret_cast<const float*>(img)[e] + 1.0f) * 127.5f;
+        u = (int)fminf(fmaxf(t, 0.f), 255.f);  // clamp, then .to(torch.uint8) truncates
+      }
+      ss += (long)u * coef[ox * ksize + x];
+    }
+    tmp[(((long)b * H + y) * OW + ox) * 3 + c] = clip8(ss);
+  }
+}
+
 // vertical resample + centre crop + rescale + normalise + patchify:
 //   out[(b * PP + py * np + px)][c * P * P + ky * P + kx] (K padded to kpad with zeros), bf16
 __global__ void resample_v_patch_kernel(int rows, int OW, int OH, int crop, int top, int left, int P, int kpad,
@@ -449,6 +484,41 @@ int pso_clip_preprocess(int B, int H, int W, const void* img, int img_dtype, int
       H, ow, oh, size, top, left, patch, kpad, tmp, tv->d_bounds, tv->d_coef, tv->ksize, mean[0], mean[1], mean[2],
       stdv[0], stdv[1], stdv[2], (bf16_t*)out);
   return pso_check_launch("pso_clip_preprocess(v)");
+}
+
+int pso_clip_preprocess_img(int B, int H, int W, const void* img, int img_kind, int size, int patch, int kpad,
+                            const float* mean, const float* stdv, void* out, void* ws, size_t ws_bytes, void* stream) {
+  PSO_ARG_CHECK(B > 0 && H > 0 && W > 0 && img && out && ws && mean && stdv,
+                "pso_clip_preprocess_img: null / bad shape");
+  PSO_ARG_CHECK(img_kind == PSO_IMG_F32 || img_kind == PSO_IMG_ELEM || img_kind == PSO_IMG_U8,
+                "pso_clip_preprocess_img: img_kind is PSO_IMG_F32, PSO_IMG_ELEM (" PSO_ELEM_NAME ") or PSO_IMG_U8");
+  PSO_ARG_CHECK(patch > 0 && size > 0 && size % patch == 0 && kpad >= 3 * patch * patch && kpad % 8 == 0,
+                "pso_clip_preprocess_img: size must be a multiple of patch, kpad >= 3 * patch^2 (multiple of 8)");
+  PSO_ARG_CHECK(ws_bytes >= pso_clip_preprocess_ws_bytes(B, H, W, size),
+                "pso_clip_preprocess_img: workspace too small");
+  // the resize geometry of pso_clip_preprocess: shortest edge -> size, centre crop size x size
+  int oh, ow;
+  if (H <= W) { oh = size; ow = (int)((long)size * W / H); }
+  else { ow = size; oh = (int)((long)size * H / W); }
+  const int top = (oh - size) / 2, left = (ow - size) / 2;
+  const ResampleTable *th, *tv;
+  int rc = get_table(W, ow, &th);
+  if (rc != PSO_OK) return rc;
+  rc = get_table(H, oh, &tv);
+  if (rc != PSO_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  uint8_t* tmp = (uint8_t*)ws;
+  const long htot = (long)H * ow * 3;
+  resample_h_img_kernel<<<dim3(cdiv(htot, 256) > 4096 ? 4096 : cdiv(htot, 256), B), 256, 0, st>>>(
+      H, W, ow, img, img_kind, th->d_bounds, th->d_coef, th->ksize, tmp);
+  rc = pso_check_launch("pso_clip_preprocess_img(h)");
+  if (rc != PSO_OK) return rc;
+  const long np = size / patch;
+  const long vtot = np * np * kpad;
+  resample_v_patch_kernel<<<dim3(cdiv(vtot, 256) > 4096 ? 4096 : cdiv(vtot, 256), B), 256, 0, st>>>(
+      H, ow, oh, size, top, left, patch, kpad, tmp, tv->d_bounds, tv->d_coef, tv->ksize, mean[0], mean[1], mean[2],
+      stdv[0], stdv[1], stdv[2], (bf16_t*)out);
+  return pso_check_launch("pso_clip_preprocess_img(v)");
 }
 
 }  // extern "C"

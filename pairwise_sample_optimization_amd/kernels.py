@@ -1564,17 +1564,25 @@ def patchify(x, P, kpad):
     return out
 
 
-def clip_preprocess(img, size, P, kpad, mean, std):
+def clip_preprocess(img, size, P, kpad, mean, std, allow_f16=False):
     """decoded images NHWC [B, H, W, 3] (bf16 / f32 in [-1, 1], or uint8) -> patch rows [B * (size/P)^2, kpad] bf16
-    (uint8 quantisation, PIL bicubic resize, centre crop, rescale, normalise)."""
+    (uint8 quantisation, PIL bicubic resize, centre crop, rescale, normalise).
+    allow_f16=True goes through pso_clip_preprocess_img, whose image kind is no dtype code: under the f16 library it
+    takes fp16, f32 and uint8 images and writes fp16 patch rows; under a bf16 library it gives the default's bits."""
     require_cuda(img)
-    _lib.require_bf16("clip_preprocess (the reward models' image path; dtype code 2 means uint8 to this entry)")
+    _lib.require_bf16_or_opt_in("clip_preprocess (the reward models' image path; dtype code 2 means uint8 to its "
+                                "default entry)", allow_f16)
     B, H, W, C = img.shape
     assert C == 3 and img.dtype in (ELEM, torch.float32, torch.uint8) and img.is_contiguous()
     ws = torch.empty(lib().pso_clip_preprocess_ws_bytes(B, H, W, size), device=img.device, dtype=torch.uint8)
     out = torch.empty((B * (size // P) ** 2, kpad), device=img.device, dtype=ELEM)
     m = (ctypes.c_float * 3)(*mean)
     sd = (ctypes.c_float * 3)(*std)
+    if allow_f16:
+        kind = {torch.uint8: _lib.IMG_U8, torch.float32: _lib.IMG_F32}.get(img.dtype, _lib.IMG_ELEM)
+        check(lib().pso_clip_preprocess_img(B, H, W, ptr(img), kind, size, P, kpad, m, sd, ptr(out), ptr(ws),
+                                            ws.numel(), stream_ptr()), "pso_clip_preprocess_img")
+        return out
     code = 2 if img.dtype == torch.uint8 else dtype_code(img)  # PSO_U8
     check(lib().pso_clip_preprocess(B, H, W, ptr(img), code, size, P, kpad, m, sd, ptr(out), ptr(ws),
                                     ws.numel(), stream_ptr()), "pso_clip_preprocess")

@@ -46,11 +46,12 @@ def encode_prompt(text_encoders, text_input_ids_list):
     return cat, pooled.reshape(B, -1)
 
 
-def sdxl_text_encoders(device, seed=0, configs=(None, None)):
+def sdxl_text_encoders(device, seed=0, configs=(None, None), allow_f16=False):
     """Random-init SDXL text encoders (CLIP ViT-L/14 text + OpenCLIP bigG/14 text with projection), synthetic
-    weights in the transformers layout (no checkpoints on this build)."""
+    weights in the transformers layout (no checkpoints on this build).  allow_f16: build them under the f16 library
+    (clip.py's opt-in; ignored under bf16)."""
     c1 = configs[0] or CLIPTextConfig.sdxl_l()
     c2 = configs[1] or CLIPTextConfig.sdxl_bigg()
     with torch.device(device):
-        e1, e2 = CLIPTextModel(c1), CLIPTextModelWithProjection(c2)
+        e1, e2 = CLIPTextModel(c1, allow_f16=allow_f16), CLIPTextModelWithProjection(c2, allow_f16=allow_f16)
     return e1.init_weights(seed), e2.init_weights(seed + 1)

@@ -19,14 +19,15 @@ from .. import kernels as K
 
 class Selector:
     def __init__(self, device, cache_dir=None, model_path=None, processor_path=None, seed=0, text_config=None,
-                 vision_config=None):
+                 vision_config=None, allow_f16=False):
+        """allow_f16: build and run the model under the f16 library (clip.py's opt-in; ignored under bf16)."""
         self.device = torch.device(device)
         if model_path is not None:
-            self.model = CLIPModel.from_pretrained(model_path).to(self.device)
+            self.model = CLIPModel.from_pretrained(model_path, allow_f16=allow_f16).to(self.device)
         else:
             with torch.device(self.device):
                 self.model = CLIPModel(text_config or CLIPTextConfig.pickscore_h(),
-                                       vision_config or CLIPVisionConfig())
+                                       vision_config or CLIPVisionConfig(), allow_f16=allow_f16)
             self.model.init_weights(seed)
         self.tokenizer = None
         self.mean, self.std = CLIP_MEAN, CLIP_STD
