@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PSO_ABI_VERSION 1
+#define PSO_ABI_VERSION 2
 
 #define PSO_OK 0
 #define PSO_ERR_ARG 1
@@ -460,44 +460,46 @@ int pso_split_channels(long npix, int C1, int C2, const void* in, void* y1, void
 size_t pso_grad_clip_ws_bytes(long n);
 int pso_grad_clip_coef(long n, const float* grad, float grad_scale, float max_norm, float* out_norm_coef, void* ws,
                        size_t ws_bytes, void* stream);
-int pso_adamw_step(long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
-                   float beta2, float eps, float weight_decay, int step, float grad_scale, const float* clip_coef,
-                   void* stream);
+/* Both steps (pso_adamw_step here, pso_adamw8bit_step below) take the step's scalars from three sources:
+ *   host arguments  lr, step (counts from 1: the bias corrections are formed on the host from it) and grad_scale;
+ *   clip_coef       (may be NULL) pso_grad_clip_coef's output on the device: g = grad * grad_scale * clip_coef[1];
+ *   amp_state       (may be NULL) the loss-scaler block below, 4-B aligned: g = grad * GRAD_MUL * CLIP_COEF with the
+ *                   bias corrections of STEP, all read from the state -- step, grad_scale and clip_coef are unread.
+ *                   With FOUND_INF set the step is skipped: parameters, moments / codes / absmax / 32-bit state and
+ *                   the 16-bit working copy are left untouched; zero_grad still zeroes the gradient it covers;
+ *   lr_dev          (may be NULL, with or without amp_state) a 4-B aligned device word, what pso_lr_schedule wrote,
+ *                   read once per thread in place of lr, which is unread -- the same bits for the same fp32 value.
+ *                   0 is legal: the moments / codes move, the parameters keep their bits.
+ * PSO_ERR_ARG before any launch: step < 1 without amp_state, a misaligned amp_state or lr_dev, a null buffer. */
+int pso_adamw_step(long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
+                   const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, int step,
+                   float grad_scale, const float* clip_coef, const void* amp_state, void* stream);
 /* Blockwise 8-bit AdamW (bitsandbytes AdamW8bit, the reference's default optimizer: config_sdxl_turbo_dpo.py:86
  * `use_8bit_adam = True`, T:427-435).  exp_avg_q / exp_avg_sq_q are uint8 codes [n] into the signed / unsigned dynamic
  * quantisation maps (pso_adamw8bit_maps), absmax_m / absmax_v one fp32 scale per 2048-element block
  * (pso_adamw8bit_blocks(n) of each); all zero-initialised.  Per element: dequantise with the block's previous absmax,
  * m = b1 m + (1-b1) g, v = b2 v + (1-b2) g^2, p += -lr c2/c1 * m / (sqrt(v) + c2 eps), p *= 1 - lr wd (c1 = 1-b1^t,
- * c2 = sqrt(1-b2^t)), then requantise to the nearest code against the block's new absmax.  g = grad * grad_scale *
- * clip_coef[1] (clip_coef may be NULL).  Parity unpinned (bitsandbytes is not in this image; oracle/adam8bit.py). */
+ * c2 = sqrt(1-b2^t)), then requantise to the nearest code against the block's new absmax.  g and the
+ * step scalars as described above.  Parity unpinned (bitsandbytes is not in this image; oracle/adam8bit.py).
+ * desc == NULL: uniform 2048-element blocks over [0, n), all 8-bit; takes nblk == pso_adamw8bit_blocks(n),
+ * zero_grad == 0 and exp_avg_32 == exp_avg_sq_32 == NULL.
+ * desc != NULL: the per-tensor form (what bitsandbytes does with a list of parameter tensors, T:428-448): nblk blocks
+ * described by the device table desc [nblk][4] (int64: start element, length <= 2048, 32-bit state offset or -1,
+ * unused).  The blocks restart at every tensor, so one absmax never spans two tensors; a tensor under bitsandbytes'
+ * min_8bit_size (4096 elements) keeps 32-bit state (no quantisation: m / v fp32 at exp_avg_32 / exp_avg_sq_32 + offset,
+ * same update), absmax_m / absmax_v hold one entry per table block.  Elements no block covers (alignment pads) are not
+ * touched.  zero_grad != 0: every gradient element a block covers is zeroed once it has been read (optimizer.zero_grad,
+ * T:861, folded into the step: no separate pass over the gradient).
+ * Non-finite gradient elements leave the parameter and its state unchanged.  param_bf16 (may be NULL) [n]: also
+ * receives the updated parameters rounded to bf16 (RNE) -- the working copy the UNet kernels read, without a separate
+ * cast pass.  param, grad, param_bf16 and the 32-bit state need 16-B, the code arrays 8-B alignment. */
 size_t pso_adamw8bit_blocks(long n);
 void pso_adamw8bit_maps(float* signed_map, float* unsigned_map);
-int pso_adamw8bit_step(long n, float* param, const float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q,
-                       float* absmax_m, float* absmax_v, float lr, float beta1, float beta2, float eps,
-                       float weight_decay, int step, float grad_scale, const float* clip_coef, void* stream);
-/* The same step that also writes the updated parameters rounded to bf16 (RNE) into param_bf16 [n] (16-B aligned; NULL
- * = pso_adamw8bit_step): the bf16 working copy the UNet kernels read, without a separate cast pass. */
-int pso_adamw8bit_step_bf16(long n, float* param, void* param_bf16, const float* grad, uint8_t* exp_avg_q,
-                            uint8_t* exp_avg_sq_q, float* absmax_m, float* absmax_v, float lr, float beta1, float beta2,
-                            float eps, float weight_decay, int step, float grad_scale, const float* clip_coef,
-                            void* stream);
-/* Per-tensor form (what bitsandbytes does with a list of parameter tensors, T:428-448): nblk blocks described by the
- * device table desc [nblk][4] (int64: start element, length <= 2048, 32-bit state offset or -1, unused).  The blocks
- * restart at every tensor, so one absmax never spans two tensors; a tensor under bitsandbytes' min_8bit_size (4096
- * elements) keeps 32-bit state (no quantisation: m / v fp32 at exp_avg_32 / exp_avg_sq_32 + offset, same update),
- * absmax_m / absmax_v hold one entry per table block.  Elements no block covers (alignment pads) are not touched.
- * Non-finite gradient elements leave the parameter and its state unchanged.  param_bf16 may be NULL. */
-int pso_adamw8bit_step_blocks(long n, int nblk, const long* desc, float* param, void* param_bf16, const float* grad,
-                              uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m, float* absmax_v,
-                              float* exp_avg_32, float* exp_avg_sq_32, float lr, float beta1, float beta2, float eps,
-                              float weight_decay, int step, float grad_scale, const float* clip_coef, void* stream);
-/* = pso_adamw8bit_step_blocks, and every gradient element a block covers is zeroed once it has been read
- * (optimizer.zero_grad, T:861, folded into the step: no separate pass over the gradient).  Pads are not touched. */
-int pso_adamw8bit_step_blocks_zero_grad(long n, int nblk, const long* desc, float* param, void* param_bf16,
-                                        float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
-                                        float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, float lr,
-                                        float beta1, float beta2, float eps, float weight_decay, int step,
-                                        float grad_scale, const float* clip_coef, void* stream);
+int pso_adamw8bit_step(long n, int nblk, const long* desc, float* param, void* param_bf16, float* grad,
+                       int zero_grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
+                       float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32,
+                       float lr, const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
+                       int step, float grad_scale, const float* clip_coef, const void* amp_state, void* stream);
 int pso_zero_f32(long n, float* x, void* stream);
 /* Device-resident dynamic loss scaling for fp16 training (torch.amp.GradScaler's state machine, T:303-319, 344-350,
  * with its state on the device as GradScaler keeps it: no host read-back in an optimizer step, every entry below is
@@ -511,7 +513,7 @@ int pso_zero_f32(long n, float* x, void* stream);
  *   PSO_AMP_STEP           i32  applied optimizer steps (AdamW's `step`; a skipped step does not count)
  *   PSO_AMP_SKIPPED        i32  optimizer steps skipped for a non-finite gradient
  *   PSO_AMP_NORM           f32  last gradient norm (unscaled)          PSO_AMP_CLIP_COEF  f32  its clip coefficient
- *   PSO_AMP_GRAD_MUL       f32  grad_scale / S of the last unscale: the factor the _amp steps put on the gradient
+ *   PSO_AMP_GRAD_MUL       f32  grad_scale / S of the last unscale: a step's gradient factor under amp_state
  *   PSO_AMP_BC1, PSO_AMP_BC2_SQRT  f32  1 - b1^step, sqrt(1 - b2^step) in fp32 (pso_adamw_step's formulas)
  *   PSO_AMP_C1, PSO_AMP_C2         f32  the same in double, rounded (the 8-bit step's c1 / c2)
  *   the remaining words are reserved (zero).
@@ -519,10 +521,7 @@ int pso_zero_f32(long n, float* x, void* stream);
  *   grad_scale / S -- into NORM, CLIP_COEF and GRAD_MUL; FOUND_INF = !isfinite(norm); a finite norm advances STEP and
  *   writes that step's BC1 .. C2.  ws as for pso_grad_clip_coef.
  * pso_amp_update: FOUND_INF -> S *= backoff_factor, tracker = 0, SKIPPED += 1; otherwise tracker += 1 and, when it
- *   reaches growth_interval, S *= growth_factor and tracker = 0 (GradScaler.update).
- * pso_adamw_step_amp / pso_adamw8bit_step_blocks[_zero_grad]_amp: the steps above on grad * GRAD_MUL * CLIP_COEF with
- *   the bias corrections of STEP, all read from the state.  FOUND_INF: parameters, moments / codes / absmax / 32-bit
- *   state and the 16-bit working copy are left untouched; the zero_grad form still zeroes the gradient it covers. */
+ *   reaches growth_interval, S *= growth_factor and tracker = 0 (GradScaler.update). */
 #define PSO_AMP_WORDS 16
 #define PSO_AMP_SCALE 0
 #define PSO_AMP_INV_SCALE 1
@@ -540,17 +539,6 @@ int pso_zero_f32(long n, float* x, void* stream);
 int pso_amp_unscale_clip(long n, const float* grad, float grad_scale, float max_norm, float beta1, float beta2,
                          void* amp_state, void* ws, size_t ws_bytes, void* stream);
 int pso_amp_update(void* amp_state, float growth_factor, float backoff_factor, int growth_interval, void* stream);
-int pso_adamw_step_amp(long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
-                       float beta1, float beta2, float eps, float weight_decay, const void* amp_state, void* stream);
-int pso_adamw8bit_step_blocks_amp(long n, int nblk, const long* desc, float* param, void* param_bf16,
-                                  const float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
-                                  float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, float lr, float beta1,
-                                  float beta2, float eps, float weight_decay, const void* amp_state, void* stream);
-int pso_adamw8bit_step_blocks_zero_grad_amp(long n, int nblk, const long* desc, float* param, void* param_bf16,
-                                            float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
-                                            float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, float lr,
-                                            float beta1, float beta2, float eps, float weight_decay,
-                                            const void* amp_state, void* stream);
 /* Learning-rate schedule with warm-up, evaluated on the device: the six lambdas of diffusers' optimization.py that the
  * DreamBooth script reaches through get_scheduler(--lr_scheduler, --lr_warmup_steps, --lr_num_cycles, --lr_power)
  * (DB:586-612, 1614-1621), stepped once per applied optimizer step (DB:1962-1963).  Parity with diffusers itself is
@@ -571,10 +559,7 @@ int pso_adamw8bit_step_blocks_zero_grad_amp(long n, int nblk, const long* desc, 
  *   World size cancels (the script scales w and T by num_processes, accelerate steps the scheduler num_processes times
  *   per optimizer step): pass the unscaled counts.  PSO_ERR_ARG: unknown kind, lr_out NULL, base_lr <= 0, step < 1
  *   without a state, warmup < 0, polynomial with total <= warmup or base_lr <= 1e-7.
- * pso_adamw_step_amp_lr / pso_adamw8bit_step_blocks[_zero_grad]_amp_lr: = their _amp siblings above with the step's lr
- *   read from the device word lr_dev (4-B aligned; what pso_lr_schedule wrote) once per thread in place of the float
- *   argument -- the same bits for the same fp32 value.  0 is legal: the moments / codes move, the parameters keep
- *   their bits. */
+ *   pso_adamw_step, pso_adamw8bit_step and pso_prodigy_step_lr read the word as their lr_dev. */
 #define PSO_LR_CONSTANT 0
 #define PSO_LR_CONSTANT_WITH_WARMUP 1
 #define PSO_LR_LINEAR 2
@@ -583,19 +568,6 @@ int pso_adamw8bit_step_blocks_zero_grad_amp(long n, int nblk, const long* desc, 
 #define PSO_LR_POLYNOMIAL 5
 int pso_lr_schedule(int kind, double base_lr, int warmup, int total, int num_cycles, double power,
                     const void* amp_state, int step, float* lr_out, void* stream);
-int pso_adamw_step_amp_lr(long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
-                          const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
-                          const void* amp_state, void* stream);
-int pso_adamw8bit_step_blocks_amp_lr(long n, int nblk, const long* desc, float* param, void* param_bf16,
-                                     const float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
-                                     float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, const float* lr_dev,
-                                     float beta1, float beta2, float eps, float weight_decay, const void* amp_state,
-                                     void* stream);
-int pso_adamw8bit_step_blocks_zero_grad_amp_lr(long n, int nblk, const long* desc, float* param, void* param_bf16,
-                                               float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q,
-                                               float* absmax_m, float* absmax_v, float* exp_avg_32,
-                                               float* exp_avg_sq_32, const float* lr_dev, float beta1, float beta2,
-                                               float eps, float weight_decay, const void* amp_state, void* stream);
 /* Prodigy (prodigyopt 1.0's Prodigy.step, one parameter group): the DreamBooth script's --optimizer prodigy, DB:622-673
  * (its own branch, DB:1479-1510, validates the flags and never builds the optimizer).  Parity with the package is
  * unpinned (prodigyopt is not available here; tests/prodigy_ref.py restates the arithmetic below).  Per-element state on

@@ -156,28 +156,14 @@ SIGNATURES = {
     "pso_lora_merge": (ci, [ci, vp, vp, vp]),
     "pso_gather_rows": (ci, [cl, cl, vp, vp, vp, vp]),
     "pso_grad_clip_coef": (ci, [cl, vp, cf, cf, vp, vp, csz, vp]),
-    "pso_adamw_step": (ci, [cl, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, vp, vp]),
+    "pso_adamw_step": (ci, [cl, vp, vp, vp, vp, cf, vp, cf, cf, cf, cf, ci, cf, vp, vp, vp]),
     "pso_adamw8bit_blocks": (csz, [cl]),
     "pso_adamw8bit_maps": (None, [vp, vp]),
-    "pso_adamw8bit_step": (ci, [cl, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, vp, vp]),
-    "pso_adamw8bit_step_bf16": (ci, [cl, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, vp, vp]),
-    "pso_adamw8bit_step_blocks": (ci, [cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf,
-                                       vp, vp]),
-    "pso_adamw8bit_step_blocks_zero_grad": (ci, [cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf,
-                                                 ci, cf, vp, vp]),
+    "pso_adamw8bit_step": (ci, [cl, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, cf, vp, cf, cf, cf, cf, ci, cf, vp,
+                                vp, vp]),
     "pso_amp_unscale_clip": (ci, [cl, vp, cf, cf, cf, cf, vp, vp, csz, vp]),
     "pso_amp_update": (ci, [vp, cf, cf, ci, vp]),
-    "pso_adamw_step_amp": (ci, [cl, vp, vp, vp, vp, cf, cf, cf, cf, cf, vp, vp]),
-    "pso_adamw8bit_step_blocks_amp": (ci, [cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, vp,
-                                           vp]),
-    "pso_adamw8bit_step_blocks_zero_grad_amp": (ci, [cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf,
-                                                     cf, vp, vp]),
     "pso_lr_schedule": (ci, [ci, cd, ci, ci, ci, cd, vp, ci, vp, vp]),
-    "pso_adamw_step_amp_lr": (ci, [cl, vp, vp, vp, vp, vp, cf, cf, cf, cf, vp, vp]),
-    "pso_adamw8bit_step_blocks_amp_lr": (ci, [cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, vp,
-                                              vp]),
-    "pso_adamw8bit_step_blocks_zero_grad_amp_lr": (ci, [cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf,
-                                                        cf, vp, vp]),
     "pso_prodigy_step_lr": (ci, [cl, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, cf, cf, vp, vp, vp,
                                  csz, vp]),
     "pso_prodigy_ws_bytes": (csz, [cl]),

@@ -90,7 +90,7 @@ __global__ void clip_coef_kernel(int nparts, const double* __restrict__ part, fl
 // unscale + norm + clip of the all-reduced gradient: the same fp32 expression as clip_coef_kernel with
 // scale = grad_scale / S (S a power of two: the product grad_scale * inv_scale is that quotient exactly).  A finite
 // norm advances the applied-step count and leaves that step's bias-correction constants in the state: bc1 / bc2_sqrt
-// by pso_adamw_step's fp32 formulas, c1 / c2 by adam8_launch's double ones.
+// by pso_adamw_step's fp32 formulas, c1 / c2 by pso_adamw8bit_step's double ones.
 __global__ void amp_unscale_clip_kernel(int nparts, const double* __restrict__ part, float grad_scale, float max_norm,
                                         float beta1, float beta2, float* __restrict__ st) {
   const double s = sum_partials(nparts, part);
@@ -196,29 +196,35 @@ __device__ __forceinline__ void adamw_body(long n, float* __restrict__ p, const 
   }
 }
 
+// The scalars of one AdamW / 8-bit AdamW step from their three nullable device sources, resolved once per thread and
+// the same over the grid; the arguments arrive holding the host-formed values.
+//   clip    pso_grad_clip_coef's output: s (the host's grad_scale) takes its coefficient
+//   amp     the loss-scaler state: s and the bias corrections (words w1, w2) come from it, clip is not read; returns
+//           false on a skipped step (FOUND_INF)
+//   lr_dev  the word pso_lr_schedule wrote: lr comes from it; 0 is legal (the moments move, the parameters keep
+//           their bits)
+__device__ __forceinline__ bool step_scalars(const float* __restrict__ clip, const float* __restrict__ amp,
+                                             const float* __restrict__ lr_dev, int w1, int w2, float& lr, float& s,
+                                             float& c1, float& c2) {
+  if (amp) {
+    if (AMP_CI(amp, PSO_AMP_FOUND_INF)) return false;
+    s = amp[PSO_AMP_GRAD_MUL] * amp[PSO_AMP_CLIP_COEF];
+    c1 = amp[w1];
+    c2 = amp[w2];
+  } else {
+    s = s * (clip ? clip[1] : 1.0f);
+  }
+  if (lr_dev) lr = lr_dev[0];
+  return true;
+}
+
 __global__ void adamw_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, float lr, float b1, float b2, float eps, float wd, float bc1,
-                             float bc2_sqrt, float gscale, const float* __restrict__ clip) {
-  adamw_body(n, p, g, m, v, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale * (clip ? clip[1] : 1.0f));
-}
-
-// the same step with the gradient factor, the bias corrections and the inf-skip read from the loss-scaler state
-__global__ void adamw_amp_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                 float* __restrict__ v, float lr, float b1, float b2, float eps, float wd,
-                                 const float* __restrict__ st) {
-  if (AMP_CI(st, PSO_AMP_FOUND_INF)) return;  // skipped step: parameters and moments untouched
-  adamw_body(n, p, g, m, v, lr, b1, b2, eps, wd, st[PSO_AMP_BC1], st[PSO_AMP_BC2_SQRT],
-             st[PSO_AMP_GRAD_MUL] * st[PSO_AMP_CLIP_COEF]);
-}
-
-// ... and with the step's learning rate read from a device word (pso_lr_schedule wrote it); 0 is legal: the moments
-// move, the parameters keep their bits
-__global__ void adamw_amp_lr_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                    float* __restrict__ v, const float* __restrict__ lr_dev, float b1, float b2,
-                                    float eps, float wd, const float* __restrict__ st) {
-  if (AMP_CI(st, PSO_AMP_FOUND_INF)) return;
-  adamw_body(n, p, g, m, v, lr_dev[0], b1, b2, eps, wd, st[PSO_AMP_BC1], st[PSO_AMP_BC2_SQRT],
-             st[PSO_AMP_GRAD_MUL] * st[PSO_AMP_CLIP_COEF]);
+                             float bc2_sqrt, float gscale, const float* __restrict__ clip,
+                             const float* __restrict__ amp, const float* __restrict__ lr_dev) {
+  // skipped step: parameters and moments untouched
+  if (!step_scalars(clip, amp, lr_dev, PSO_AMP_BC1, PSO_AMP_BC2_SQRT, lr, gscale, bc1, bc2_sqrt)) return;
+  adamw_body(n, p, g, m, v, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
 }
 
 // ---- blockwise 8-bit AdamW (bitsandbytes AdamW8bit: the reference default, config_sdxl_turbo_dpo.py:86, T:427-435)
@@ -278,8 +284,7 @@ __device__ __forceinline__ int adam8_node(int i) {
 // LAY = element-to-thread mapping inside a block.  0: thread t owns the 8 consecutive elements 8t .. 8t + 7 (each
 // 16-B access instruction of a wave spans 2 KB with 16-B gaps); 1: thread t owns 4t .. 4t + 3 and 1024 + 4t .. +3, so
 // every access instruction of a wave covers one contiguous range.  Per-block results are the same bits either way.
-// s = the factor on the gradient read.  The body of adamw8bit_kernel (host arguments) and adamw8bit_amp_kernel (the
-// loss-scaler state's).
+// s = the factor on the gradient read.
 template <int LAY>
 __device__ __forceinline__ void adamw8bit_body(
     long n, float* __restrict__ p, float* g, uint8_t* __restrict__ qm, uint8_t* __restrict__ qv,
@@ -443,60 +448,34 @@ __device__ __forceinline__ void adamw8bit_body(
   if (t == 0) { am[blk] = nm; av[blk] = nv; }
 }
 
+// The step scalars as step_scalars resolves them.  eps_c2, step_size and decay are what pso_adamw8bit_step forms on the
+// host from its own lr, c1 and c2; they stand when neither amp nor lr_dev is given -- with either, they are formed
+// here by the same expressions (fp32, the decay in double, as there).  A skipped step (amp, FOUND_INF) leaves the
+// parameters, codes, absmax, 32-bit state and working copy untouched; with zero_grad it still zeroes the gradient
+// elements its blocks cover (the host path zeroes the gradient of a skipped step too).
 template <int LAY>
 __global__ __launch_bounds__(256) void adamw8bit_kernel(
     long n, float* __restrict__ p, float* g, uint8_t* __restrict__ qm, uint8_t* __restrict__ qv,
-    float* __restrict__ am, float* __restrict__ av, float b1, float omb1, float b2, float omb2, float eps_c2,
-    float step_size, float decay, float gscale, const float* __restrict__ clip, bf16_t* __restrict__ pw,
-    const long* __restrict__ desc, float* __restrict__ m32, float* __restrict__ v32, int zero_grad, Adam8Maps maps) {
-  adamw8bit_body<LAY>(n, p, g, qm, qv, am, av, b1, omb1, b2, omb2, eps_c2, step_size, decay,
-                      gscale * (clip ? clip[1] : 1.0f), pw, desc, m32, v32, zero_grad, maps);
-}
-
-// the per-tensor step with the gradient factor, c1 / c2 and the inf-skip read from the loss-scaler state.  A skipped
-// step leaves the parameters, codes, absmax, 32-bit state and working copy untouched; with zero_grad it still zeroes
-// the gradient elements its blocks cover (the host path zeroes the gradient of a skipped step too).
-// the skipped step of the two kernels below; true when the step is skipped (uniform over the workgroup)
-__device__ __forceinline__ bool adam8_amp_skip(const float* __restrict__ st, float* g, const long* __restrict__ desc,
-                                               int zero_grad) {
-  if (!AMP_CI(st, PSO_AMP_FOUND_INF)) return false;
-  if (zero_grad) {
-    const long base = desc[4 * (long)blockIdx.x], end = base + desc[4 * (long)blockIdx.x + 1];
-    for (long i = base + threadIdx.x; i < end; i += blockDim.x) g[i] = 0.f;
+    float* __restrict__ am, float* __restrict__ av, float b1, float omb1, float b2, float omb2, float eps, float wd,
+    float lr, float c1, float c2, float eps_c2, float step_size, float decay, float gscale,
+    const float* __restrict__ clip, const float* __restrict__ amp, const float* __restrict__ lr_dev,
+    bf16_t* __restrict__ pw, const long* __restrict__ desc, float* __restrict__ m32, float* __restrict__ v32,
+    int zero_grad, Adam8Maps maps) {
+#pragma clang fp contract(off)
+  if (!step_scalars(clip, amp, lr_dev, PSO_AMP_C1, PSO_AMP_C2, lr, gscale, c1, c2)) {
+    if (zero_grad) {
+      const long base = desc[4 * (long)blockIdx.x], end = base + desc[4 * (long)blockIdx.x + 1];
+      for (long i = base + threadIdx.x; i < end; i += blockDim.x) g[i] = 0.f;
+    }
+    return;
   }
-  return true;
-}
-
-template <int LAY>
-__global__ __launch_bounds__(256) void adamw8bit_amp_kernel(
-    long n, float* __restrict__ p, float* g, uint8_t* __restrict__ qm, uint8_t* __restrict__ qv,
-    float* __restrict__ am, float* __restrict__ av, float b1, float omb1, float b2, float omb2, float eps, float lr,
-    float decay, const float* __restrict__ st, bf16_t* __restrict__ pw, const long* __restrict__ desc,
-    float* __restrict__ m32, float* __restrict__ v32, int zero_grad, Adam8Maps maps) {
-#pragma clang fp contract(off)
-  if (adam8_amp_skip(st, g, desc, zero_grad)) return;
-  const float c1 = st[PSO_AMP_C1], c2 = st[PSO_AMP_C2];
-  const float step_size = (-lr) * c2 / c1;  // adam8_launch's host expressions, in fp32 as there
-  adamw8bit_body<LAY>(n, p, g, qm, qv, am, av, b1, omb1, b2, omb2, c2 * eps, step_size, decay,
-                      st[PSO_AMP_GRAD_MUL] * st[PSO_AMP_CLIP_COEF], pw, desc, m32, v32, zero_grad, maps);
-}
-
-// ... and with the step's learning rate read from a device word: step_size and the decay factor, which adam8_launch
-// forms on the host from its lr argument, are formed here by the same expressions (the decay in double, as there)
-template <int LAY>
-__global__ __launch_bounds__(256) void adamw8bit_amp_lr_kernel(
-    long n, float* __restrict__ p, float* g, uint8_t* __restrict__ qm, uint8_t* __restrict__ qv,
-    float* __restrict__ am, float* __restrict__ av, float b1, float omb1, float b2, float omb2, float eps,
-    const float* __restrict__ lr_dev, float wd, const float* __restrict__ st, bf16_t* __restrict__ pw,
-    const long* __restrict__ desc, float* __restrict__ m32, float* __restrict__ v32, int zero_grad, Adam8Maps maps) {
-#pragma clang fp contract(off)
-  if (adam8_amp_skip(st, g, desc, zero_grad)) return;
-  const float lr = lr_dev[0];
-  const float c1 = st[PSO_AMP_C1], c2 = st[PSO_AMP_C2];
-  const float step_size = (-lr) * c2 / c1;
-  const float decay = (float)(1.0 - (double)lr * wd);
-  adamw8bit_body<LAY>(n, p, g, qm, qv, am, av, b1, omb1, b2, omb2, c2 * eps, step_size, decay,
-                      st[PSO_AMP_GRAD_MUL] * st[PSO_AMP_CLIP_COEF], pw, desc, m32, v32, zero_grad, maps);
+  if (amp || lr_dev) {
+    step_size = (-lr) * c2 / c1;
+    decay = (float)(1.0 - (double)lr * wd);
+    eps_c2 = c2 * eps;
+  }
+  adamw8bit_body<LAY>(n, p, g, qm, qv, am, av, b1, omb1, b2, omb2, eps_c2, step_size, decay, gscale, pw, desc, m32,
+                      v32, zero_grad, maps);
 }
 
 // bitsandbytes.functional.create_dynamic_map(signed, max_exponent_bits = 7, total_bits = 8), float32 like the
@@ -574,15 +553,20 @@ int pso_grad_clip_coef(long n, const float* grad, float grad_scale, float max_no
   return pso_check_launch("pso_grad_clip_coef");
 }
 
-int pso_adamw_step(long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
-                   float beta2, float eps, float weight_decay, int step, float grad_scale, const float* clip_coef,
-                   void* stream) {
-  PSO_ARG_CHECK(param && grad && exp_avg && exp_avg_sq && step >= 1, "pso_adamw_step: bad args");
+int pso_adamw_step(long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
+                   const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, int step,
+                   float grad_scale, const float* clip_coef, const void* amp_state, void* stream) {
+  PSO_ARG_CHECK(param && grad && exp_avg && exp_avg_sq, "pso_adamw_step: bad args");
+  PSO_ARG_CHECK(amp_state || step >= 1, "pso_adamw_step: step counts from 1 (got %d) when no amp_state is given",
+                step);
+  PSO_ARG_CHECK((((uintptr_t)amp_state | (uintptr_t)lr_dev) & 3) == 0,
+                "pso_adamw_step: amp_state and lr_dev must be 4-B aligned (or NULL)");
+  // unread with amp_state (the state holds that step's)
   const float bc1 = 1.0f - powf(beta1, (float)step);
   const float bc2 = 1.0f - powf(beta2, (float)step);
-  adamw_kernel<<<nblocks(n), OPT_THREADS, 0, (hipStream_t)stream>>>(n, param, grad, exp_avg, exp_avg_sq, lr, beta1,
-                                                                    beta2, eps, weight_decay, bc1, sqrtf(bc2),
-                                                                    grad_scale, clip_coef);
+  adamw_kernel<<<nblocks(n), OPT_THREADS, 0, (hipStream_t)stream>>>(
+      n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2), grad_scale, clip_coef,
+      (const float*)amp_state, lr_dev);
   return pso_check_launch("pso_adamw_step");
 }
 
@@ -605,28 +589,6 @@ int pso_amp_update(void* amp_state, float growth_factor, float backoff_factor, i
   amp_update_kernel<<<1, 64, 0, (hipStream_t)stream>>>((float*)amp_state, growth_factor, backoff_factor,
                                                       growth_interval);
   return pso_check_launch("pso_amp_update");
-}
-
-int pso_adamw_step_amp(long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
-                       float beta1, float beta2, float eps, float weight_decay, const void* amp_state, void* stream) {
-  PSO_ARG_CHECK(param && grad && exp_avg && exp_avg_sq && amp_state && ((uintptr_t)amp_state & 3) == 0,
-                "pso_adamw_step_amp: bad args");
-  adamw_amp_kernel<<<nblocks(n), OPT_THREADS, 0, (hipStream_t)stream>>>(n, param, grad, exp_avg, exp_avg_sq, lr,
-                                                                        beta1, beta2, eps, weight_decay,
-                                                                        (const float*)amp_state);
-  return pso_check_launch("pso_adamw_step_amp");
-}
-
-int pso_adamw_step_amp_lr(long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
-                          const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
-                          const void* amp_state, void* stream) {
-  PSO_ARG_CHECK(param && grad && exp_avg && exp_avg_sq && amp_state && ((uintptr_t)amp_state & 3) == 0 && lr_dev &&
-                    ((uintptr_t)lr_dev & 3) == 0,
-                "pso_adamw_step_amp_lr: bad args");
-  adamw_amp_lr_kernel<<<nblocks(n), OPT_THREADS, 0, (hipStream_t)stream>>>(n, param, grad, exp_avg, exp_avg_sq, lr_dev,
-                                                                           beta1, beta2, eps, weight_decay,
-                                                                           (const float*)amp_state);
-  return pso_check_launch("pso_adamw_step_amp_lr");
 }
 
 int pso_lr_schedule(int kind, double base_lr, int warmup, int total, int num_cycles, double power,
@@ -652,20 +614,30 @@ void pso_adamw8bit_maps(float* signed_map, float* unsigned_map) {
   adam8_dynamic_map(false, unsigned_map);
 }
 
-static int adam8_launch(long n, int nblk, float* param, void* param_bf16, float* grad, int zero_grad, uint8_t* exp_avg_q,
-                        uint8_t* exp_avg_sq_q, float* absmax_m, float* absmax_v, const long* desc, float* m32,
-                        float* v32, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                        float grad_scale, const float* clip_coef, void* stream, const float* amp = nullptr,
-                        const float* lr_dev = nullptr) {
+int pso_adamw8bit_step(long n, int nblk, const long* desc, float* param, void* param_bf16, float* grad, int zero_grad,
+                       uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m, float* absmax_v, float* exp_avg_32,
+                       float* exp_avg_sq_32, float lr, const float* lr_dev, float beta1, float beta2, float eps,
+                       float weight_decay, int step, float grad_scale, const float* clip_coef, const void* amp_state,
+                       void* stream) {
+  PSO_ARG_CHECK(param && grad && exp_avg_q && exp_avg_sq_q && absmax_m && absmax_v && n > 0 && nblk >= 0,
+                "pso_adamw8bit_step: bad args");
+  PSO_ARG_CHECK(amp_state || step >= 1, "pso_adamw8bit_step: step counts from 1 (got %d) when no amp_state is given",
+                step);
+  PSO_ARG_CHECK((((uintptr_t)amp_state | (uintptr_t)lr_dev) & 3) == 0,
+                "pso_adamw8bit_step: amp_state and lr_dev must be 4-B aligned (or NULL)");
+  PSO_ARG_CHECK(desc || (zero_grad == 0 && !exp_avg_32 && !exp_avg_sq_32 && nblk == (int)pso_adamw8bit_blocks(n)),
+                "pso_adamw8bit_step: desc == NULL (uniform blocks) takes zero_grad == 0, no 32-bit state and "
+                "nblk == pso_adamw8bit_blocks(n)");
+  PSO_ARG_CHECK((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)param_bf16 | (uintptr_t)exp_avg_32 |
+                  (uintptr_t)exp_avg_sq_32) & 15) == 0 && (((uintptr_t)exp_avg_q | (uintptr_t)exp_avg_sq_q) & 7) == 0,
+                "pso_adamw8bit_step: param / grad / param_bf16 / 32-bit state need 16-B, the code arrays 8-B alignment");
   static Adam8Maps maps = [] {
     Adam8Maps m;
     adam8_dynamic_map(true, m.s);
     adam8_dynamic_map(false, m.u);
     return m;
   }();
-  // amp != nullptr: step, grad_scale and clip_coef are unused -- c1 / c2, the gradient factor and the inf-skip come
-  // from the loss-scaler state on the device (adamw8bit_amp_kernel); lr_dev != nullptr (with amp): lr is unused too --
-  // the device word holds it (adamw8bit_amp_lr_kernel)
+  // the host-form scalars; the kernel replaces what amp_state / lr_dev hold on the device
   const double b1 = beta1, b2 = beta2;
   const float c1 = (float)(1.0 - std::pow(b1, step));
   const float c2 = (float)std::sqrt(1.0 - std::pow(b2, step));
@@ -684,22 +656,9 @@ static int adam8_launch(long n, int nblk, float* param, void* param_bf16, float*
   const hipStream_t st = (hipStream_t)stream;
   const float omb1 = (float)(1.0 - b1), omb2 = (float)(1.0 - b2);
 #define PSO_ADAM8_ARGS                                                                                                   \
-  n, param, grad, exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, beta1, omb1, beta2, omb2, c2 * eps, step_size, decay,     \
-      grad_scale, clip_coef, (bf16_t*)param_bf16, desc, m32, v32, zero_grad, maps
-#define PSO_ADAM8_AMP_ARGS                                                                                               \
-  n, param, grad, exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, beta1, omb1, beta2, omb2, eps, lr, decay, amp,            \
-      (bf16_t*)param_bf16, desc, m32, v32, zero_grad, maps
-  if (amp && lr_dev) {
-    adamw8bit_amp_lr_kernel<ADAM8_LAYOUT_DEFAULT><<<nblk, 256, 0, st>>>(
-        n, param, grad, exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, beta1, omb1, beta2, omb2, eps, lr_dev,
-        weight_decay, amp, (bf16_t*)param_bf16, desc, m32, v32, zero_grad, maps);
-    return pso_check_launch("pso_adamw8bit_step_amp_lr");
-  }
-  if (amp) {
-    adamw8bit_amp_kernel<ADAM8_LAYOUT_DEFAULT><<<nblk, 256, 0, st>>>(PSO_ADAM8_AMP_ARGS);
-    return pso_check_launch("pso_adamw8bit_step_amp");
-  }
-#undef PSO_ADAM8_AMP_ARGS
+  n, param, grad, exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, beta1, omb1, beta2, omb2, eps, weight_decay, lr, c1, c2,  \
+      c2 * eps, step_size, decay, grad_scale, clip_coef, (const float*)amp_state, lr_dev, (bf16_t*)param_bf16, desc,     \
+      exp_avg_32, exp_avg_sq_32, zero_grad, maps
 #ifdef PSO_BENCH_KNOBS
   if (lay)
     adamw8bit_kernel<1><<<nblk, 256, 0, st>>>(PSO_ADAM8_ARGS);
@@ -711,105 +670,6 @@ static int adam8_launch(long n, int nblk, float* param, void* param_bf16, float*
 #endif
 #undef PSO_ADAM8_ARGS
   return pso_check_launch("pso_adamw8bit_step");
-}
-
-int pso_adamw8bit_step_bf16(long n, float* param, void* param_bf16, const float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q,
-                       float* absmax_m, float* absmax_v, float lr, float beta1, float beta2, float eps,
-                       float weight_decay, int step, float grad_scale, const float* clip_coef, void* stream) {
-  PSO_ARG_CHECK(param && grad && exp_avg_q && exp_avg_sq_q && absmax_m && absmax_v && step >= 1 && n > 0,
-                "pso_adamw8bit_step_bf16: bad args");
-  PSO_ARG_CHECK((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)param_bf16) & 15) == 0 && (((uintptr_t)exp_avg_q | (uintptr_t)exp_avg_sq_q) & 7) == 0,
-                "pso_adamw8bit_step_bf16: param / grad / param_bf16 need 16-B, the code arrays 8-B alignment");
-  return adam8_launch(n, (int)pso_adamw8bit_blocks(n), param, param_bf16, const_cast<float*>(grad), 0, exp_avg_q, exp_avg_sq_q, absmax_m,
-                      absmax_v, nullptr, nullptr, nullptr, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
-                      clip_coef, stream);
-}
-
-static int adam8_blocks(const char* who, long n, int nblk, const long* desc, float* param, void* param_bf16,
-                        float* grad, int zero_grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
-                        float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, float lr, float beta1, float beta2,
-                        float eps, float weight_decay, int step, float grad_scale, const float* clip_coef,
-                        void* stream, const float* amp = nullptr, const float* lr_dev = nullptr) {
-  PSO_ARG_CHECK(param && grad && exp_avg_q && exp_avg_sq_q && absmax_m && absmax_v && step >= 1 && n > 0 &&
-                    nblk >= 0 && (nblk == 0 || desc),
-                "%s: bad args", who);
-  PSO_ARG_CHECK((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)param_bf16 | (uintptr_t)exp_avg_32 |
-                  (uintptr_t)exp_avg_sq_32) & 15) == 0 && (((uintptr_t)exp_avg_q | (uintptr_t)exp_avg_sq_q) & 7) == 0,
-                "%s: param / grad / param_bf16 / 32-bit state need 16-B, the code arrays 8-B alignment", who);
-  return adam8_launch(n, nblk, param, param_bf16, grad, zero_grad, exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, desc,
-                      exp_avg_32, exp_avg_sq_32, lr, beta1, beta2, eps, weight_decay, step, grad_scale, clip_coef,
-                      stream, amp, lr_dev);
-}
-
-int pso_adamw8bit_step_blocks(long n, int nblk, const long* desc, float* param, void* param_bf16, const float* grad,
-                              uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m, float* absmax_v,
-                              float* exp_avg_32, float* exp_avg_sq_32, float lr, float beta1, float beta2, float eps,
-                              float weight_decay, int step, float grad_scale, const float* clip_coef, void* stream) {
-  return adam8_blocks("pso_adamw8bit_step_blocks", n, nblk, desc, param, param_bf16, const_cast<float*>(grad), 0,
-                      exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, exp_avg_32, exp_avg_sq_32, lr, beta1, beta2, eps,
-                      weight_decay, step, grad_scale, clip_coef, stream);
-}
-
-int pso_adamw8bit_step_blocks_zero_grad(long n, int nblk, const long* desc, float* param, void* param_bf16,
-                                        float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
-                                        float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, float lr,
-                                        float beta1, float beta2, float eps, float weight_decay, int step,
-                                        float grad_scale, const float* clip_coef, void* stream) {
-  return adam8_blocks("pso_adamw8bit_step_blocks_zero_grad", n, nblk, desc, param, param_bf16, grad, 1, exp_avg_q,
-                      exp_avg_sq_q, absmax_m, absmax_v, exp_avg_32, exp_avg_sq_32, lr, beta1, beta2, eps,
-                      weight_decay, step, grad_scale, clip_coef, stream);
-}
-
-int pso_adamw8bit_step_blocks_amp(long n, int nblk, const long* desc, float* param, void* param_bf16,
-                                  const float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
-                                  float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, float lr, float beta1,
-                                  float beta2, float eps, float weight_decay, const void* amp_state, void* stream) {
-  PSO_ARG_CHECK(amp_state && ((uintptr_t)amp_state & 3) == 0, "pso_adamw8bit_step_blocks_amp: no amp_state");
-  return adam8_blocks("pso_adamw8bit_step_blocks_amp", n, nblk, desc, param, param_bf16, const_cast<float*>(grad), 0,
-                      exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, exp_avg_32, exp_avg_sq_32, lr, beta1, beta2, eps,
-                      weight_decay, 1, 1.0f, nullptr, stream, (const float*)amp_state);
-}
-
-int pso_adamw8bit_step_blocks_zero_grad_amp(long n, int nblk, const long* desc, float* param, void* param_bf16,
-                                            float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
-                                            float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, float lr,
-                                            float beta1, float beta2, float eps, float weight_decay,
-                                            const void* amp_state, void* stream) {
-  PSO_ARG_CHECK(amp_state && ((uintptr_t)amp_state & 3) == 0, "pso_adamw8bit_step_blocks_zero_grad_amp: no amp_state");
-  return adam8_blocks("pso_adamw8bit_step_blocks_zero_grad_amp", n, nblk, desc, param, param_bf16, grad, 1, exp_avg_q,
-                      exp_avg_sq_q, absmax_m, absmax_v, exp_avg_32, exp_avg_sq_32, lr, beta1, beta2, eps,
-                      weight_decay, 1, 1.0f, nullptr, stream, (const float*)amp_state);
-}
-
-int pso_adamw8bit_step_blocks_amp_lr(long n, int nblk, const long* desc, float* param, void* param_bf16,
-                                     const float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q, float* absmax_m,
-                                     float* absmax_v, float* exp_avg_32, float* exp_avg_sq_32, const float* lr_dev,
-                                     float beta1, float beta2, float eps, float weight_decay, const void* amp_state,
-                                     void* stream) {
-  PSO_ARG_CHECK(amp_state && ((uintptr_t)amp_state & 3) == 0 && lr_dev && ((uintptr_t)lr_dev & 3) == 0,
-                "pso_adamw8bit_step_blocks_amp_lr: no amp_state or no lr_dev (4-B aligned)");
-  return adam8_blocks("pso_adamw8bit_step_blocks_amp_lr", n, nblk, desc, param, param_bf16, const_cast<float*>(grad),
-                      0, exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, exp_avg_32, exp_avg_sq_32, 0.0f, beta1, beta2,
-                      eps, weight_decay, 1, 1.0f, nullptr, stream, (const float*)amp_state, lr_dev);
-}
-
-int pso_adamw8bit_step_blocks_zero_grad_amp_lr(long n, int nblk, const long* desc, float* param, void* param_bf16,
-                                               float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q,
-                                               float* absmax_m, float* absmax_v, float* exp_avg_32,
-                                               float* exp_avg_sq_32, const float* lr_dev, float beta1, float beta2,
-                                               float eps, float weight_decay, const void* amp_state, void* stream) {
-  PSO_ARG_CHECK(amp_state && ((uintptr_t)amp_state & 3) == 0 && lr_dev && ((uintptr_t)lr_dev & 3) == 0,
-                "pso_adamw8bit_step_blocks_zero_grad_amp_lr: no amp_state or no lr_dev (4-B aligned)");
-  return adam8_blocks("pso_adamw8bit_step_blocks_zero_grad_amp_lr", n, nblk, desc, param, param_bf16, grad, 1,
-                      exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, exp_avg_32, exp_avg_sq_32, 0.0f, beta1, beta2, eps,
-                      weight_decay, 1, 1.0f, nullptr, stream, (const float*)amp_state, lr_dev);
-}
-
-int pso_adamw8bit_step(long n, float* param, const float* grad, uint8_t* exp_avg_q, uint8_t* exp_avg_sq_q,
-                       float* absmax_m, float* absmax_v, float lr, float beta1, float beta2, float eps,
-                       float weight_decay, int step, float grad_scale, const float* clip_coef, void* stream) {
-  return pso_adamw8bit_step_bf16(n, param, nullptr, grad, exp_avg_q, exp_avg_sq_q, absmax_m, absmax_v, lr, beta1,
-                                 beta2, eps, weight_decay, step, grad_scale, clip_coef, stream);
 }
 
 int pso_zero_f32(long n, float* x, void* stream) {

@@ -928,10 +928,27 @@ def grad_clip_coef(grad, max_norm, grad_scale=1.0, out=None):
     return out
 
 
-def adamw_step(param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, step, grad_scale=1.0, clip=None):
-    check(lib().pso_adamw_step(param.numel(), ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), float(lr),
-                               float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step),
-                               float(grad_scale), ptr(clip), stream_ptr()), "pso_adamw_step")
+def _step_source(who, lr, step, amp_state):
+    """(lr, lr_dev, step) as pso_adamw_step / pso_adamw8bit_step take them.  lr: a Python float, or a one-element
+    float32 device tensor (the word lr_schedule wrote; the step reads its lr there).  amp_state: an
+    amp.DeviceLossScaler's state -- the gradient factor, the bias corrections and the inf-skip come from it, and step,
+    grad_scale and clip are not read; without it `step` (counting from 1) is required."""
+    if amp_state is not None:
+        _check_amp_state(amp_state)
+    elif step is None:
+        raise _lib.PsoLibError(f"{who} needs step (counting from 1) or amp_state")
+    lr, lr_dev = (0.0, ptr(_check_lr_word(lr))) if torch.is_tensor(lr) else (float(lr), None)
+    return lr, lr_dev, 0 if step is None else int(step)
+
+
+def adamw_step(param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, step=None, grad_scale=1.0, clip=None,
+               amp_state=None):
+    """One fp32 AdamW step (pso_adamw_step); lr, step and amp_state as _step_source describes them."""
+    require_cuda(param, grad, exp_avg, exp_avg_sq)
+    lr, lr_dev, step = _step_source("adamw_step", lr, step, amp_state)
+    check(lib().pso_adamw_step(param.numel(), ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), lr, lr_dev,
+                               float(betas[0]), float(betas[1]), float(eps), float(weight_decay), step,
+                               float(grad_scale), ptr(clip), ptr(amp_state), stream_ptr()), "pso_adamw_step")
 
 
 class Adam8State:
@@ -1068,28 +1085,27 @@ class Adam8State:
         return out
 
 
-def adamw8bit_step(param, grad, state, lr, betas, eps, weight_decay, step, grad_scale=1.0, clip=None, out_bf16=None,
-                   zero_grad=False):
-    """One 8-bit AdamW step on the flat fp32 param; out_bf16 (same numel, bf16) also receives the updated parameters
-    rounded to bf16 (the working copy), in the same pass.  zero_grad (per-tensor block tables only): the step also
-    zeroes the gradient elements its blocks cover after reading them; returns whether it did."""
+def adamw8bit_step(param, grad, state, lr, betas, eps, weight_decay, step=None, grad_scale=1.0, clip=None,
+                   out_bf16=None, zero_grad=False, amp_state=None):
+    """One 8-bit AdamW step on the flat fp32 param (pso_adamw8bit_step); out_bf16 (same numel, bf16) also receives the
+    updated parameters rounded to bf16 (the working copy), in the same pass.  lr, step and amp_state as _step_source
+    describes them; amp_state takes a per-tensor block table.  zero_grad (per-tensor block tables only): the step also
+    zeroes the gradient elements its blocks cover after reading them -- on a step the loss scaler skips too; returns
+    whether it did."""
     require_cuda(param, grad)
+    lr, lr_dev, step = _step_source("adamw8bit_step", lr, step, amp_state)
+    if amp_state is not None and state.desc is None:
+        raise _lib.PsoLibError("adamw8bit_step with amp_state needs a per-tensor block table "
+                               "(Adam8State(segments=...))")
     if out_bf16 is not None:
         assert out_bf16.dtype == ELEM and out_bf16.numel() == param.numel() and out_bf16.is_contiguous()
-    if state.desc is not None:
-        fn = "pso_adamw8bit_step_blocks_zero_grad" if zero_grad else "pso_adamw8bit_step_blocks"
-        check(getattr(lib(), fn)(param.numel(), state.nblk, ptr(state.desc), ptr(param), ptr(out_bf16),
-                                              ptr(grad), ptr(state.qm), ptr(state.qv), ptr(state.am), ptr(state.av),
-                                              ptr(state.m32), ptr(state.v32), float(lr), float(betas[0]),
-                                              float(betas[1]), float(eps), float(weight_decay), int(step),
-                                              float(grad_scale), ptr(clip), stream_ptr()), fn)
-        return zero_grad
-    check(lib().pso_adamw8bit_step_bf16(param.numel(), ptr(param), ptr(out_bf16), ptr(grad), ptr(state.qm),
-                                        ptr(state.qv), ptr(state.am), ptr(state.av), float(lr), float(betas[0]),
-                                        float(betas[1]), float(eps), float(weight_decay), int(step), float(grad_scale),
-                                        ptr(clip), stream_ptr()),
-          "pso_adamw8bit_step_bf16")
-    return False
+    zero_grad = bool(zero_grad) and state.desc is not None
+    check(lib().pso_adamw8bit_step(param.numel(), state.nblk, ptr(state.desc), ptr(param), ptr(out_bf16), ptr(grad),
+                                   int(zero_grad), ptr(state.qm), ptr(state.qv), ptr(state.am), ptr(state.av),
+                                   ptr(state.m32), ptr(state.v32), lr, lr_dev, float(betas[0]), float(betas[1]),
+                                   float(eps), float(weight_decay), step, float(grad_scale), ptr(clip),
+                                   ptr(amp_state), stream_ptr()), "pso_adamw8bit_step")
+    return zero_grad
 
 
 # ---- device-resident loss scaling (amp.DeviceLossScaler): `amp_state` is its int32 [AMP_WORDS] state tensor ----------
@@ -1140,43 +1156,6 @@ def lr_schedule(sched, out, step=None, amp_state=None):
                                 int(sched.num_cycles), float(sched.power), ptr(amp_state),
                                 0 if step is None else int(step), ptr(out), stream_ptr()), "pso_lr_schedule")
     return out
-
-
-def adamw_step_amp(param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, amp_state):
-    """adamw_step with the gradient factor, the step's bias corrections and the inf-skip read from the state.  lr: a
-    Python float, or a one-element float32 device tensor (pso_adamw_step_amp_lr reads the step's lr there)."""
-    require_cuda(param, grad, exp_avg, exp_avg_sq)
-    _check_amp_state(amp_state)
-    if torch.is_tensor(lr):
-        check(lib().pso_adamw_step_amp_lr(param.numel(), ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq),
-                                          ptr(_check_lr_word(lr)), float(betas[0]), float(betas[1]), float(eps),
-                                          float(weight_decay), ptr(amp_state), stream_ptr()), "pso_adamw_step_amp_lr")
-        return
-    check(lib().pso_adamw_step_amp(param.numel(), ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), float(lr),
-                                   float(betas[0]), float(betas[1]), float(eps), float(weight_decay), ptr(amp_state),
-                                   stream_ptr()), "pso_adamw_step_amp")
-
-
-def adamw8bit_step_amp(param, grad, state, lr, betas, eps, weight_decay, amp_state, out_bf16=None, zero_grad=False):
-    """adamw8bit_step (per-tensor block tables only) driven by the loss-scaler state; returns whether the gradient
-    was zeroed -- it is on a skipped step too.  lr: a Python float, or a one-element float32 device tensor (the word
-    lr_schedule wrote) for the `_lr` entries, which read the step's lr on the device."""
-    require_cuda(param, grad)
-    _check_amp_state(amp_state)
-    if state.desc is None:
-        raise _lib.PsoLibError("adamw8bit_step_amp needs a per-tensor block table (Adam8State(segments=...))")
-    if out_bf16 is not None:
-        assert out_bf16.dtype == ELEM and out_bf16.numel() == param.numel() and out_bf16.is_contiguous()
-    fn = "pso_adamw8bit_step_blocks_zero_grad_amp" if zero_grad else "pso_adamw8bit_step_blocks_amp"
-    if torch.is_tensor(lr):
-        fn, lr = fn + "_lr", ptr(_check_lr_word(lr))
-    else:
-        lr = float(lr)
-    check(getattr(lib(), fn)(param.numel(), state.nblk, ptr(state.desc), ptr(param), ptr(out_bf16), ptr(grad),
-                             ptr(state.qm), ptr(state.qv), ptr(state.am), ptr(state.av), ptr(state.m32),
-                             ptr(state.v32), lr, float(betas[0]), float(betas[1]), float(eps),
-                             float(weight_decay), ptr(amp_state), stream_ptr()), fn)
-    return zero_grad
 
 
 class ProdigyState:

@@ -391,45 +391,15 @@ def init_optimizer_state(tr, unet, optimizer="adamw", use_8bit_adam=False, prodi
     tr.exp_avg_sq = None if use_8bit_adam else torch.zeros_like(master)
 
 
-def _amp_optimizer_step(tr, scaler, scale):
-    """lora_optimizer_step after the all-reduce with a DeviceLossScaler: unscale / norm / clip -> AdamW -> scale
-    update -> zero -> refresh, every decision (inf-skip, step count, back-off and growth) taken by the kernels on the
-    scaler's state block.  Nothing is read back; a skipped step still refreshes the (unchanged) working copies."""
-    master, grad, refresh = trainable(tr.unet)
-    st = scaler.state
-    K.amp_unscale_clip(grad, tr.max_grad_norm, st, tr.betas, grad_scale=scale)
-    # a schedule: the step's lr is evaluated on the device from the state's applied-step count (a skipped step leaves
-    # the word as it was) and the `_lr` entries read it there; without one the host float goes in as it always has
-    lr = tr.lr
-    if getattr(tr, "lr_schedule", None) is not None:
-        lr = K.lr_schedule(tr.lr_schedule, tr.lr_word, amp_state=st)
-    cast = True
-    if getattr(tr, "prodigy", None) is not None:
-        zeroed = False
-        K.prodigy_step(master, grad, tr.prodigy, lr, tr.betas, tr.adam_eps, tr.wd, amp_state=st, **tr.prodigy_opts)
-    elif getattr(tr, "adam8", None) is not None:
-        work = _work_copy(tr.unet, master)
-        zeroed = K.adamw8bit_step_amp(master, grad, tr.adam8, lr, tr.betas, tr.adam_eps, tr.wd, st, out_bf16=work,
-                                      zero_grad=True)
-        cast = work is None
-    else:
-        zeroed = False
-        K.adamw_step_amp(master, grad, tr.exp_avg, tr.exp_avg_sq, lr, tr.betas, tr.adam_eps, tr.wd, st)
-    if getattr(tr, "ema", None) is not None:  # once per call, skipped or not (lora_optimizer_step's docstring)
-        tr.ema.step()
-    K.amp_update(st, scaler.growth_factor, scaler.backoff_factor, scaler.growth_interval)
-    if not zeroed:
-        K.zero_(grad)
-    refresh(cast=cast)
-
-
 def lora_optimizer_step(tr):
     """accelerator.backward's sync step + clip_grad_norm_ + optimizer.step + zero_grad (T:857-861, DB:1953-1964) on
     the flat LoRA bucket of tr.unet: RCCL all-reduce -> global-norm clip coefficient -> fused AdamW (clip and 1/world
     folded into the gradient read) -> zero -> refresh the bf16 working copies.  tr carries exp_avg, exp_avg_sq,
     opt_step, clip_buf, lr, betas, adam_eps, wd, max_grad_norm, pg and, when the last backward of the window already
     issued the bucketed all-reduce (tr.sync_armed), the GradBuckets to finish.  fp16 training: tr.scaler is an
-    amp.LossScaler (the norm is read back, one sync) or an amp.DeviceLossScaler (_amp_optimizer_step: no read-back).
+    amp.LossScaler (the norm is read back, one sync) or an amp.DeviceLossScaler (unscale / norm / clip -> step -> scale
+    update, every decision -- inf-skip, step count, back-off and growth -- taken by the kernels on the scaler's state
+    block: nothing is read back, and a skipped step still refreshes the unchanged working copies).
     tr.lr_schedule (None = the fixed rate tr.lr): the step runs at lr_schedule.lr(k), k = the steps applied before it.
     tr.ema (None = off; init_ema): ema.EMAModel.step() once per call, after the optimizer kernel -- and the opposite of
     the schedule's rule: the schedule counts APPLIED steps, so a step the loss scaler skips does not advance it, while
@@ -444,49 +414,61 @@ def lora_optimizer_step(tr):
     else:
         scale = allreduce_grads(grad, tr.pg, getattr(tr, "allreduce_dtype", None))
     scaler = getattr(tr, "scaler", None)
-    if isinstance(scaler, DeviceLossScaler):
-        return _amp_optimizer_step(tr, scaler, scale)
-    if scaler is not None:
-        # fp16 loss scaling (amp.LossScaler): the backward ran on loss * S, so unscale in the gradient read.  The norm
-        # of the all-reduced gradient is read back -- the one sync per optimizer step, where GradScaler.step syncs --
-        # and every rank sees the same value.  Non-finite: skip the step whole (parameters, moments / 8-bit state and
-        # opt_step untouched), drop the gradient, back the scale off (accelerate's inf-skip, T:344-350).
-        scale = scale / scaler.scale
-    K.grad_clip_coef(grad, tr.max_grad_norm, grad_scale=scale, out=tr.clip_buf)
-    if scaler is not None:
-        found_inf = not math.isfinite(float(tr.clip_buf[0]))
-        scaler.update(found_inf)
-        if found_inf:
-            K.zero_(grad)
-            if getattr(tr, "ema", None) is not None:  # the EMA counts windows, not applied steps
-                tr.ema.step()
-            return
-    tr.opt_step += 1
-    # a schedule (DB:1614-1621, stepped at DB:1962-1963): this step runs at lr(opt_step - 1) -- the host knows the
-    # count here, so AdamW takes the value as the float it always took; Prodigy's host-argument entry rejects the 0 a
-    # warm-up starts at, so its lr goes through the device word (one single-lane launch)
     sched = getattr(tr, "lr_schedule", None)
-    lr = tr.lr if sched is None else sched.lr(tr.opt_step - 1)
-    cast = True
-    if getattr(tr, "prodigy", None) is not None:  # optimizer="prodigy": k, d and dlr stay on the device
-        zeroed = False
-        if sched is not None:
+    prodigy = getattr(tr, "prodigy", None)
+    device_scaler = isinstance(scaler, DeviceLossScaler)
+    # `src` = where the optimizer kernel takes the step's scalars from; `lr` = a float, or the device word
+    if device_scaler:
+        src = dict(amp_state=scaler.state)
+        K.amp_unscale_clip(grad, tr.max_grad_norm, scaler.state, tr.betas, grad_scale=scale)
+        # a schedule: the step's lr is evaluated on the device from the state's applied-step count (a skipped step
+        # leaves the word as it was) and the kernels read it there; without one the host float goes in
+        lr = tr.lr if sched is None else K.lr_schedule(sched, tr.lr_word, amp_state=scaler.state)
+    else:
+        if scaler is not None:
+            # fp16 loss scaling (amp.LossScaler): the backward ran on loss * S, so unscale in the gradient read.  The
+            # norm of the all-reduced gradient is read back -- the one sync per optimizer step, where GradScaler.step
+            # syncs -- and every rank sees the same value.  Non-finite: skip the step whole (parameters, moments /
+            # 8-bit state and opt_step untouched), drop the gradient, back the scale off (accelerate's inf-skip,
+            # T:344-350).
+            scale = scale / scaler.scale
+        K.grad_clip_coef(grad, tr.max_grad_norm, grad_scale=scale, out=tr.clip_buf)
+        if scaler is not None:
+            found_inf = not math.isfinite(float(tr.clip_buf[0]))
+            scaler.update(found_inf)
+            if found_inf:
+                K.zero_(grad)
+                if getattr(tr, "ema", None) is not None:  # the EMA counts windows, not applied steps
+                    tr.ema.step()
+                return
+        tr.opt_step += 1
+        src = dict(step=tr.opt_step, grad_scale=scale, clip=tr.clip_buf)
+        # a schedule (DB:1614-1621, stepped at DB:1962-1963): this step runs at lr(opt_step - 1) -- the host knows the
+        # count here, so AdamW takes the value as the float it always took; Prodigy's host-argument entry rejects the
+        # 0 a warm-up starts at, so its lr goes through the device word (one single-lane launch)
+        if sched is None:
+            lr = tr.lr
+        elif prodigy is not None:
             lr = K.lr_schedule(sched, tr.lr_word, step=tr.opt_step)
-        K.prodigy_step(master, grad, tr.prodigy, lr, tr.betas, tr.adam_eps, tr.wd, grad_scale=scale,
-                       clip=tr.clip_buf, **tr.prodigy_opts)
+        else:
+            lr = sched.lr(tr.opt_step - 1)
+    cast, zeroed = True, False
+    if prodigy is not None:  # optimizer="prodigy": k, d and dlr stay on the device, so it takes no `step`
+        src.pop("step", None)
+        K.prodigy_step(master, grad, prodigy, lr, tr.betas, tr.adam_eps, tr.wd, **src, **tr.prodigy_opts)
     elif getattr(tr, "adam8", None) is not None:  # train.use_8bit_adam: bitsandbytes AdamW8bit (T:427-435)
         work = _work_copy(tr.unet, master)  # the step also writes the bf16 working copy (no separate cast pass)
         # with a per-tensor block table the step also zeroes the gradient it reads (the pads between tensors are
         # zero from allocation and no kernel writes them)
-        zeroed = K.adamw8bit_step(master, grad, tr.adam8, lr, tr.betas, tr.adam_eps, tr.wd, tr.opt_step,
-                                  grad_scale=scale, clip=tr.clip_buf, out_bf16=work, zero_grad=True)
+        zeroed = K.adamw8bit_step(master, grad, tr.adam8, lr, tr.betas, tr.adam_eps, tr.wd, out_bf16=work,
+                                  zero_grad=True, **src)
         cast = work is None
     else:
-        zeroed = False
-        K.adamw_step(master, grad, tr.exp_avg, tr.exp_avg_sq, lr, tr.betas, tr.adam_eps, tr.wd, tr.opt_step,
-                     grad_scale=scale, clip=tr.clip_buf)
-    if getattr(tr, "ema", None) is not None:
+        K.adamw_step(master, grad, tr.exp_avg, tr.exp_avg_sq, lr, tr.betas, tr.adam_eps, tr.wd, **src)
+    if getattr(tr, "ema", None) is not None:  # once per call, skipped or not (the docstring)
         tr.ema.step()
+    if device_scaler:
+        K.amp_update(scaler.state, scaler.growth_factor, scaler.backoff_factor, scaler.growth_interval)
     if not zeroed:
         K.zero_(grad)
     refresh(cast=cast)

@@ -29,7 +29,7 @@ def test_library_exports_every_declared_symbol():
         assert name in exported, name
         assert name in _lib.SIGNATURES, f"{name} not bound in _lib.SIGNATURES"
         getattr(l, name)
-    assert l.pso_abi_version() == 1
+    assert l.pso_abi_version() == 2
 
 
 def test_bound_signatures_match_header_arity():

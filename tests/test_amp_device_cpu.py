@@ -13,8 +13,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "pairwise_sample_optimization_amd")
-NEW = ["pso_amp_unscale_clip", "pso_amp_update", "pso_adamw_step_amp", "pso_adamw8bit_step_blocks_amp",
-       "pso_adamw8bit_step_blocks_zero_grad_amp"]
+NEW = ["pso_amp_unscale_clip", "pso_amp_update", "pso_adamw_step", "pso_adamw8bit_step"]
 
 
 def test_new_symbols_are_declared_exported_and_bound():
@@ -30,7 +29,7 @@ def test_new_symbols_are_declared_exported_and_bound():
         assert name in decl and name in _lib.SIGNATURES, name
         assert len([a for a in decl[name].split(",") if a.strip()]) == len(_lib.SIGNATURES[name][1]), name
         assert getattr(_lib.lib(), name).argtypes == _lib.SIGNATURES[name][1]
-    assert _lib.lib().pso_abi_version() == 1
+    assert _lib.lib().pso_abi_version() == 2
     # the word indices of the state block, header against binding
     words = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define PSO_AMP_(\w+) (\d+)", h)}
     assert words.pop("WORDS") == _lib.AMP_WORDS == 16

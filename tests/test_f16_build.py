@@ -55,7 +55,7 @@ import torch
 import pairwise_sample_optimization_amd as pkg
 from pairwise_sample_optimization_amd import _lib
 l = _lib.lib()
-assert l.pso_abi_version() == 1
+assert l.pso_abi_version() == 2
 print("path", _lib.LIB_PATH)
 print("elem", l.pso_elem_dtype())
 print("compute", pkg.compute_dtype())

@@ -151,7 +151,7 @@ def test_skipped_step_leaves_everything_unchanged(cuda):
     sc = _scaler(cuda, init_scale=1024.0)
     p0, m0, v0 = p.clone(), m.clone(), v.clone()
     K.amp_unscale_clip(grad, 1.0, sc.state, BETAS)
-    K.adamw_step_amp(p, grad, m, v, LR, BETAS, EPS, WD, sc.state)
+    K.adamw_step(p, grad, m, v, LR, BETAS, EPS, WD, amp_state=sc.state)
     K.amp_update(sc.state, sc.growth_factor, sc.backoff_factor, sc.growth_interval)
     for a, b in ((p, p0), (m, m0), (v, v0)):
         assert torch.equal(_bits(a), _bits(b))
@@ -164,7 +164,7 @@ def test_skipped_step_leaves_everything_unchanged(cuda):
         work = K.cast_f32_bf16(p)
         warm = torch.randn(n, device=cuda, generator=g) * 1e-2
         K.amp_unscale_clip(warm, 1.0, sc.state, BETAS)  # one applied step first: non-trivial codes / absmax / m32
-        K.adamw8bit_step_amp(p, warm, st, LR, BETAS, EPS, WD, sc.state, out_bf16=work)
+        K.adamw8bit_step(p, warm, st, LR, BETAS, EPS, WD, amp_state=sc.state, out_bf16=work)
         assert sc.step == 1 and st.am.abs().max().item() > 0 and st.m32.abs().max().item() > 0
         before = {k: t.clone() for k, t in st.tensors().items()}
         p0, w0 = p.clone(), work.clone()
@@ -172,7 +172,8 @@ def test_skipped_step_leaves_everything_unchanged(cuda):
         grad[2048 * 5 + 1002] = float("inf")
         g0 = grad.clone()
         K.amp_unscale_clip(grad, 1.0, sc.state, BETAS)
-        zeroed = K.adamw8bit_step_amp(p, grad, st, LR, BETAS, EPS, WD, sc.state, out_bf16=work, zero_grad=zero_grad)
+        zeroed = K.adamw8bit_step(p, grad, st, LR, BETAS, EPS, WD, amp_state=sc.state, out_bf16=work,
+                                  zero_grad=zero_grad)
         K.amp_update(sc.state, sc.growth_factor, sc.backoff_factor, sc.growth_interval)
         assert zeroed == zero_grad
         assert torch.equal(_bits(p), _bits(p0)) and torch.equal(work.view(torch.int16), w0.view(torch.int16))
@@ -189,7 +190,7 @@ def test_skipped_step_leaves_everything_unchanged(cuda):
 
 def test_applied_steps_match_the_host_argument_entries(cuda):
     """Steps 1..3 on the same inputs through the `_amp` entries (S = 1024, 1/world = 1/3, clipping on) and through
-    pso_adamw_step / pso_adamw8bit_step_blocks_zero_grad with host arguments.  m / v, codes, absmax and the 32-bit
+    pso_adamw_step / pso_adamw8bit_step (zero_grad) with host arguments.  m / v, codes, absmax and the 32-bit
     state do not depend on the bias correction: bit-identical.  Parameters: the device evaluates the bias-correction
     formulas with its own powf / pow, so they are held to 1e-6 * max|p| (the bar of the 8-bit restatement test,
     DESIGN.md section 7 #4); the number of differing elements is printed."""
@@ -205,7 +206,7 @@ def test_applied_steps_match_the_host_argument_entries(cuda):
     for step in (1, 2, 3):
         grad = torch.randn(n, device=cuda, generator=g) * S
         K.amp_unscale_clip(grad, max_norm, sc.state, BETAS, grad_scale=gs)
-        K.adamw_step_amp(p_a, grad, m_a, v_a, LR, BETAS, EPS, WD, sc.state)
+        K.adamw_step(p_a, grad, m_a, v_a, LR, BETAS, EPS, WD, amp_state=sc.state)
         K.amp_update(sc.state, sc.growth_factor, sc.backoff_factor, sc.growth_interval)
         clip = K.grad_clip_coef(grad, max_norm, grad_scale=gs / S)
         K.adamw_step(p_h, grad, m_h, v_h, LR, BETAS, EPS, WD, step, grad_scale=gs / S, clip=clip)
@@ -225,7 +226,7 @@ def test_applied_steps_match_the_host_argument_entries(cuda):
         grad = torch.randn(n, device=cuda, generator=g) * S * 1e-2
         g_h = grad.clone()
         K.amp_unscale_clip(grad, max_norm, sc.state, BETAS, grad_scale=gs)
-        K.adamw8bit_step_amp(p_a, grad, st_a, LR, BETAS, EPS, WD, sc.state, out_bf16=w_a, zero_grad=True)
+        K.adamw8bit_step(p_a, grad, st_a, LR, BETAS, EPS, WD, amp_state=sc.state, out_bf16=w_a, zero_grad=True)
         K.amp_update(sc.state, sc.growth_factor, sc.backoff_factor, sc.growth_interval)
         clip = K.grad_clip_coef(g_h, max_norm, grad_scale=gs / S)
         K.adamw8bit_step(p_h, g_h, st_h, LR, BETAS, EPS, WD, step, grad_scale=gs / S, clip=clip, out_bf16=w_h,

@@ -879,7 +879,7 @@ def test_adamw8bit_vs_restatement(cuda, n):
 
 
 def test_adamw8bit_per_tensor_vs_restatement(cuda):
-    """pso_adamw8bit_step_blocks: bitsandbytes' per-tensor semantics on a flat buffer of mixed-size tensors (T:428-448,
+    """pso_adamw8bit_step with a block table: bitsandbytes' per-tensor semantics on a flat buffer of mixed-size tensors (T:428-448,
     ADVICE r3): blocks restart at every tensor, tensors under 4096 elements keep 32-bit state, alignment pads between
     tensors are never touched, and non-finite gradient elements (injected at step 3) leave the parameter and its state
     unchanged -- against oracle/adam8bit.adamw8bit_step_tensors over 5 steps (parity unpinned: no bitsandbytes)."""
@@ -914,7 +914,7 @@ def test_adamw8bit_per_tensor_vs_restatement(cuda):
             gr[[3, 5001, 7000, 12000]] = [np.nan, np.inf, -np.inf, np.nan]
         gr[pads] = 7.0  # never read: the pads are no block's
         gd = torch.tensor(gr, device=cuda)
-        # odd steps also zero the gradient they read (pso_adamw8bit_step_blocks_zero_grad, optimizer.zero_grad T:861)
+        # odd steps also zero the gradient they read (pso_adamw8bit_step's zero_grad, optimizer.zero_grad T:861)
         zg = K_.adamw8bit_step(pd, gd, st, lr, (b1, b2), eps, wd, step, out_bf16=wb, zero_grad=step % 2 == 1)
         gk = gd.cpu().numpy()
         assert zg == (step % 2 == 1) and np.array_equal(gk[pads], gr[pads])

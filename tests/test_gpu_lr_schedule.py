@@ -1,13 +1,13 @@
 """GPU cases of the learning-rate schedule on the default (bf16) library: pso_lr_schedule against the host LrSchedule,
-the device-lr (`_lr`) optimizer entries against their host-argument siblings, and the trainers' optimizer step with a
-schedule.  fp32 / fp64 / integer arithmetic only; the device-scaler trainer cases run under PSO_LIB=f16
+the optimizer steps with the lr in a device word against the same steps with the float, and the trainers' optimizer
+step with a schedule.  fp32 / fp64 / integer arithmetic only; the device-scaler trainer cases run under PSO_LIB=f16
 (tests/test_gpu_lr_schedule_f16.py).
 
 Bounds.  pso_lr_schedule evaluates the host's double expressions on the device and rounds to fp32 once, as the host
 does.  Where the expression is integer conversions, IEEE divisions and one multiplication (constant, the warm-up ramp,
 the linear decay) both sides form the same double: bit-equal.  Where it calls cos or pow, the device's double result may
 differ from libm's in its last bits, which moves the fp32 rounding by at most one step: 1 fp32 ulp.
-The `_lr` entries run the kernels of their siblings with the lr loaded instead of passed: bit-identical.
+The steps with a device lr word run the host-argument kernels with the lr loaded instead of passed: bit-identical.
 The trainer against its K.adamw_step mirror: the same entry with the same arguments, bit-identical; against CPU
 torch.optim.AdamW with the transformers scheduler: the 1e-5 absolute bound of
 tests/test_gpu_trainer.py::test_optimizer_step_matches_torch_adamw."""
@@ -117,7 +117,7 @@ def test_schedule_argument_errors(cuda):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# 2. the `_lr` entries against their host-argument siblings
+# 2. the lr in a device word against the float argument
 # ----------------------------------------------------------------------------------------------------------------------
 def _word(cuda, lr):
     return torch.tensor([lr], dtype=torch.float32, device=cuda)
@@ -152,8 +152,8 @@ def test_adamw_lr_entry_is_the_host_argument_entry(cuda, lr, misaligned):
         a = [torch.empty(N + 1, device=cuda)[1:].copy_(t) for t in a]
         b = [torch.empty(N + 1, device=cuda)[1:].copy_(t) for t in b]
         assert all(t.data_ptr() % 16 == 4 for t in a + b)
-    K.adamw_step_amp(a[0], grad, a[1], a[2], _word(cuda, lr), BETAS, EPS, WD, sc.state)
-    K.adamw_step_amp(b[0], grad, b[1], b[2], lr, BETAS, EPS, WD, sc.state)
+    K.adamw_step(a[0], grad, a[1], a[2], _word(cuda, lr), BETAS, EPS, WD, amp_state=sc.state)
+    K.adamw_step(b[0], grad, b[1], b[2], lr, BETAS, EPS, WD, amp_state=sc.state)
     for x, y, name in zip(a, b, "pmv"):
         assert torch.equal(_bits(x), _bits(y)), name
     assert not torch.equal(a[1], m) and not torch.equal(a[2], v)  # the moments moved
@@ -198,13 +198,14 @@ def test_adamw8bit_lr_entries_are_the_host_argument_entries(cuda, lr, zero_grad)
         work = K.cast_f32_bf16(p)
         _set_words(sc, STEP=0, SCALE=1.0, INV_SCALE=1.0)
         K.amp_unscale_clip(warm, 1.0, sc.state, BETAS)  # one applied step first: non-trivial codes / absmax / m32
-        K.adamw8bit_step_amp(p, warm.clone(), st, LR, BETAS, EPS, WD, sc.state, out_bf16=work)
+        K.adamw8bit_step(p, warm.clone(), st, LR, BETAS, EPS, WD, amp_state=sc.state, out_bf16=work)
         before = {k: t.clone() for k, t in st.tensors().items()}
         p1 = p.clone()
         _set_words(sc, SCALE=1024.0, INV_SCALE=1.0 / 1024.0)
         gr = grad.clone()
         K.amp_unscale_clip(gr, 1.0, sc.state, BETAS, grad_scale=1.0 / 3.0)
-        zeroed = K.adamw8bit_step_amp(p, gr, st, lr_arg, BETAS, EPS, WD, sc.state, out_bf16=work, zero_grad=zero_grad)
+        zeroed = K.adamw8bit_step(p, gr, st, lr_arg, BETAS, EPS, WD, amp_state=sc.state, out_bf16=work,
+                                  zero_grad=zero_grad)
         assert zeroed == zero_grad
         runs.append((p, work, gr, {k: t.clone() for k, t in st.tensors().items()}, before, p1))
     (pa, wa, ga, sa, before, p1), (pb, wb, gb, sb, _, _) = runs
@@ -236,7 +237,7 @@ def test_lr_entries_skip_on_found_inf(cuda):
     sc = _amp_state(cuda, grad)
     _set_words(sc, FOUND_INF=1)
     keep = [t.clone() for t in (p, m, v, grad)]
-    K.adamw_step_amp(p, grad, m, v, word, BETAS, EPS, WD, sc.state)
+    K.adamw_step(p, grad, m, v, word, BETAS, EPS, WD, amp_state=sc.state)
     for x, y in zip((p, m, v, grad), keep):
         assert torch.equal(_bits(x), _bits(y))
     # 8-bit, both forms
@@ -247,14 +248,14 @@ def test_lr_entries_skip_on_found_inf(cuda):
         warm = torch.randn(n, device=cuda, generator=g) * 1e-2
         sc = _scaler(cuda, init_scale=1.0)
         K.amp_unscale_clip(warm, 1.0, sc.state, BETAS)
-        K.adamw8bit_step_amp(p, warm, st, word, BETAS, EPS, WD, sc.state, out_bf16=work)
+        K.adamw8bit_step(p, warm, st, word, BETAS, EPS, WD, amp_state=sc.state, out_bf16=work)
         assert st.am.abs().max().item() > 0 and st.m32.abs().max().item() > 0
         before = {k: t.clone() for k, t in st.tensors().items()}
         p1, w1 = p.clone(), work.clone()
         grad = torch.randn(n, device=cuda, generator=g)
         g0 = grad.clone()
         _set_words(sc, FOUND_INF=1)
-        K.adamw8bit_step_amp(p, grad, st, word, BETAS, EPS, WD, sc.state, out_bf16=work, zero_grad=zero_grad)
+        K.adamw8bit_step(p, grad, st, word, BETAS, EPS, WD, amp_state=sc.state, out_bf16=work, zero_grad=zero_grad)
         assert torch.equal(_bits(p), _bits(p1)) and torch.equal(work.view(torch.int16), w1.view(torch.int16))
         for k, t in st.tensors().items():
             assert torch.equal(t, before[k]), k
@@ -264,6 +265,55 @@ def test_lr_entries_skip_on_found_inf(cuda):
         else:
             assert torch.equal(_bits(grad), _bits(g0))
     assert word.item() == np.float32(LR)
+
+
+@pytest.mark.parametrize("opt", ["adamw", "adamw8bit"])
+def test_device_lr_word_without_amp_state_is_the_host_float(cuda, opt):
+    """lr from the device word with the step count, grad_scale and clip from the host (no amp_state): three steps at
+    lr 0, 1e-3 and float32(2e-4 / 3), each bit-identical to the same call with the float -- parameters, moments or
+    codes, absmax, 32-bit state and the bf16 copy.  At lr 0 the parameters keep their bits while the moments move.
+    fp32 AdamW over 4101 elements; the 8-bit step over a block table of 3000 (32-bit state) + 4101 (8-bit, a
+    5-element last block) elements."""
+    from pairwise_sample_optimization_amd import kernels as K
+    g = _gen(11)
+    lrs = [0.0, 1e-3, float(np.float32(2e-4 * (1 / 3)))]
+    segs = [(0, 3000), (3000, 4101)]
+    n = 4101 if opt == "adamw" else 3000 + 4101
+    p0 = torch.randn(n, device=cuda, generator=g) * 0.02
+    grads = [torch.randn(n, device=cuda, generator=g) * 1e-2 for _ in lrs]
+    clips = [K.grad_clip_coef(gr, 0.5, grad_scale=1.0 / 3.0) for gr in grads]
+
+    def run(as_word):
+        p, out = p0.clone(), []
+        if opt == "adamw":
+            state = {"exp_avg": torch.zeros_like(p), "exp_avg_sq": torch.zeros_like(p)}
+        else:
+            st = K.Adam8State(n, cuda, segments=segs)
+            work = K.cast_f32_bf16(p)
+            state = dict(st.tensors(), work=work)
+        for step, (lr, gr, clip) in enumerate(zip(lrs, grads, clips), 1):
+            lr_arg = _word(cuda, lr) if as_word else lr
+            gr = gr.clone()
+            if opt == "adamw":
+                K.adamw_step(p, gr, state["exp_avg"], state["exp_avg_sq"], lr_arg, BETAS, EPS, WD, step,
+                             grad_scale=1.0 / 3.0, clip=clip)
+            else:
+                K.adamw8bit_step(p, gr, st, lr_arg, BETAS, EPS, WD, step, grad_scale=1.0 / 3.0, clip=clip,
+                                 out_bf16=work, zero_grad=step == 2)
+            out.append(dict({k: t.clone() for k, t in state.items()}, param=p.clone(), grad=gr))
+        return out
+
+    word, host = run(True), run(False)
+    for step, (a, b) in enumerate(zip(word, host), 1):
+        for k in a:
+            assert torch.equal(a[k].view(torch.uint8), b[k].view(torch.uint8)), (step, k)
+    assert torch.equal(_bits(word[0]["param"]), _bits(p0))  # lr 0: the parameters keep their bits ...
+    moved = ("exp_avg_q", "exp_avg_sq_q", "exp_avg_32", "exp_avg_sq_32")
+    for k in ("exp_avg", "exp_avg_sq") if opt == "adamw" else moved:  # ... while the moments move
+        assert word[0][k].any(), k
+    assert not torch.equal(word[1]["param"], p0) and not torch.equal(word[2]["param"], word[1]["param"])
+    if opt == "adamw8bit":
+        assert word[1]["grad"].abs().max().item() == 0.0 and torch.equal(word[0]["grad"], grads[0])
 
 
 @pytest.mark.parametrize("misaligned", [False, True])

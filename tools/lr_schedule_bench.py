@@ -2,11 +2,11 @@
 
     python tools/lr_schedule_bench.py [--n 23500000] [--blocks 6] [--reps 1000] [--warmup 50] [--out FILE]
 
-The optimizer step of trainer._amp_optimizer_step on a flat fp32 buffer of n parameters (C2: LoRA r = 32 on SDXL is
-23.5 M) with the 8-bit AdamW, as two launch sequences:
-  fixed     pso_amp_unscale_clip -> pso_adamw8bit_step_blocks_zero_grad_amp (lr a host float) -> pso_amp_update
+The device-scaler optimizer step of trainer.lora_optimizer_step on a flat fp32 buffer of n parameters (C2: LoRA r = 32
+on SDXL is 23.5 M) with the 8-bit AdamW, as two launch sequences:
+  fixed     pso_amp_unscale_clip -> pso_adamw8bit_step (amp_state, zero_grad, lr a host float) -> pso_amp_update
             -- what a trainer without a schedule launches, before and after the schedule existed
-  schedule  pso_amp_unscale_clip -> pso_lr_schedule(amp_state) -> pso_adamw8bit_step_blocks_zero_grad_amp_lr
+  schedule  pso_amp_unscale_clip -> pso_lr_schedule(amp_state) -> pso_adamw8bit_step (amp_state, zero_grad, lr_dev)
             -> pso_amp_update
 Every repetition first refills the gradient from a fixed copy (the step zeroes it), in both sequences alike.  A block is
 `reps` repetitions between two device events; blocks alternate fixed / schedule; the report gives the per-step median
@@ -57,8 +57,8 @@ def main():
         step_lr = lr
         if name == "schedule":
             step_lr = K.lr_schedule(sched, r["word"], amp_state=sc.state)
-        K.adamw8bit_step_amp(r["p"], r["grad"], r["st"], step_lr, betas, eps, wd, sc.state, out_bf16=r["work"],
-                             zero_grad=True)
+        K.adamw8bit_step(r["p"], r["grad"], r["st"], step_lr, betas, eps, wd, amp_state=sc.state, out_bf16=r["work"],
+                         zero_grad=True)
         K.amp_update(sc.state, sc.growth_factor, sc.backoff_factor, sc.growth_interval)
 
     for name in runs:
